@@ -20,21 +20,25 @@ Both halves are inside the timed bracket; `value` = bytes backed / total wall ti
 §8d). The other natural reading — a growth burst of K batches with nothing unmapped — is reported as the
 variant `growth_burst` (there hipMemCreate's O(live handles) cost dominates).
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
 N > 1: this script starts its own N ranks (spawn_ranks: one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set as
 torch.distributed.run would; under such a launcher - WORLD_SIZE already set - it is a rank). The path shards with no
 data-path collective — every rank backs its own KV shard — and the only exchange is the one the
 reference has too: rank 0's offset vector is broadcast to the TP group (CollectiveFanout: one RCCL
 broadcast + one status all-reduce per step). Weak scaling: per-GPU work is fixed.
 
-At N = 1 the line also carries the geometry engines really use on ROCm (engine_llama3_8b_noncontig_*: one region per layer,
+With --full, at N = 1 the line also carries the geometry engines really use on ROCm (engine_llama3_8b_noncontig_*: one region per layer,
 K and V halves - one page id = 64 slots in 64 places; benchmarks/bench_engine_geometry.py) and, at N > 1, the shared-pool
 leg (rank 0 backs and exports page ids, the other ranks import and map them and read rank 0's signature through the mapping).
 
-Prints ONE JSON line: metric/value/unit/... + "roofline" (zero_fill_pages, HBM-bound; kernel time
-from HIP events recorded inside the library on the stream the kernel runs on) + "cpu_baseline"
-(the CPU oracle timed on the host cores, rank 0 at N = 1) + extras (p50 batch latency, per-mode
-variants, and — when oracle/_ref exists — the REAL reference's HIP path timed on the same box).
+Prints ONE JSON line: metric/value/unit/ms_per_step/... + "roofline" (zero_fill_pages, HBM-bound; kernel time
+from HIP events recorded inside the library on the stream the kernel runs on) + p50 batch latency. A plain run does
+nothing else; --full adds the legs that take runs of their own: "cpu_baseline" (the CPU oracle timed on the host cores,
+rank 0 at N = 1), the per-mode variants, the engine geometry and the compaction roofline named above, the shared-pool
+leg, and — when oracle/_ref exists — the REAL reference's HIP path timed on the same box.
+
+--dump-outputs DIR: after the run, DIR/offsets.npy, DIR/kv_after_map.npy and DIR/kv_readback.npy hold what the last
+timed step's map call gave its caller (sample_last_step); the inputs are seeded, so two builds compare array for array.
 """
 from __future__ import annotations
 
@@ -65,8 +69,17 @@ def parse_args():
                          "batch invalidates the TLBs before its pages are used; lazy (KVCACHED_ZERO_BACKFILL=false): unbacked VA "
                          "stays unmapped, a stray access faults, and neither call waits for an invalidation")
     ap.add_argument("--pool-mb", type=int, default=None, help="idle physical-handle pool cap (default: library default)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra per-mode runs at N=1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: at N=1 the growth burst of a fresh process, the per-mode variants, "
+                         "the engine geometry, the compact_blocks roofline, the shared-pool rehearsal, the CPU baseline and the "
+                         "reference's HIP path; at N > 1 the shared-pool leg. Without it the run sets up, warms up, times the steps "
+                         "and prints the line")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the extra per-mode runs at N=1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the reference's HIP path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step's map call handed its caller to DIR/<name>.npy (float32/float64): the "
+                         "offsets, a seeded sample of the bytes read through the mapping, and a seeded pattern written through "
+                         "it and read back (untimed; rank 0's pages at N > 1)")
     ap.add_argument("--backend", choices=["hip", "hybrid", "drm"], default=os.environ.get("KVCACHED_VMM_BACKEND", "drm"),
                     help="VMM backend requested for the main measurement (library default: drm; DESIGN.md §4.6/§4.7); the line "
                          "reports the one in effect after the library's self tests")
@@ -139,12 +152,14 @@ def run_steps(capi, mapper, first_batch: int, n: int, slot: int = PAGE):
 
 
 def measure(capi, device, steps, warmup, mode, pool_mb, fanout=None, barrier=None, sync=None, compound_layers=0,
-            burst=False, prefault=True, backend="drm", page=PAGE):
+            burst=False, prefault=True, backend="drm", page=PAGE, probe=None):
     """cycle (default): every step maps+zeroes one batch and unmaps it again. burst=True: `steps` batches are
     backed one after the other and only unmapped after the timed region.
     prefault: as in the bench_vmm protocol (warm-up sweeps over the whole window before the timed sweeps), every batch
     of the window is mapped and unmapped once during set-up - the state of an engine that has been running for a
-    second. prefault=False skips the sweep (the timed steps then touch VA that was never mapped)."""
+    second. prefault=False skips the sweep (the timed steps then touch VA that was never mapped).
+    probe(pool, offsets): called between the map and the unmap of the last timed step; the time it takes, up to a barrier
+    at N > 1, is taken out of the timed bracket. Its result is returned as "probe"."""
     window = max(32, steps + warmup) if burst else 32  # 64 GiB of VA
     pool = Pool(capi, device, window, mode, pool_mb, page=page, compound_layers=compound_layers, backend=backend)
     slot = pool.slot
@@ -174,13 +189,20 @@ def measure(capi, device, steps, warmup, mode, pool_mb, fanout=None, barrier=Non
             sync()
         per_map, per_unmap = [], []
         # the inputs of the timed steps are ready before the clock starts: the offsets of every batch, already in the form
-        # the boundary takes them in (an int64 array for the C ABI; the TP fan-out pickles Python lists)
-        ready = [batch_offsets((warmup + i) % window, slot=slot) for i in range(steps)]
+        # the boundary takes them in (an int64 array for the C ABI; the TP fan-out pickles Python lists). One array per batch of
+        # the window, shared by the steps that visit it (both boundaries only read them), so that set-up does not grow with steps.
         if fanout is None:
-            ready = [capi.i64_array(o) for o in ready]
+            as_input = capi.i64_array
         else:
             import numpy as np
-            ready = [np.asarray(o, dtype=np.int64) for o in ready]   # packed into the broadcast message with one copy
+            as_input = lambda o: np.asarray(o, dtype=np.int64)   # noqa: E731  packed into the broadcast message with one copy
+        batches = {}
+        for i in range(steps):
+            b = (warmup + i) % window
+            if b not in batches:
+                batches[b] = as_input(batch_offsets(b, slot=slot))
+        ready = [batches[(warmup + i) % window] for i in range(steps)]
+        probed, paused = None, 0.0
         t0 = time.perf_counter()
         for i in range(steps):
             offs = ready[i]
@@ -188,6 +210,12 @@ def measure(capi, device, steps, warmup, mode, pool_mb, fanout=None, barrier=Non
             mapper(offs)
             tb = time.perf_counter()
             per_map.append(tb - ta)
+            if probe is not None and i == steps - 1:
+                probed = probe(pool, batch_offsets((warmup + i) % window, slot=slot))
+                if barrier:
+                    barrier()
+                tc = time.perf_counter()
+                paused, tb = tc - tb, tc
             if not burst:
                 unmapper(offs)
                 per_unmap.append(time.perf_counter() - tb)
@@ -198,7 +226,7 @@ def measure(capi, device, steps, warmup, mode, pool_mb, fanout=None, barrier=Non
             sync()
         if barrier:
             barrier()
-        elapsed = time.perf_counter() - t0
+        elapsed = time.perf_counter() - t0 - paused
         st = capi.get_stats()
         c1 = [int(capi.get_option(k)) for k in (112, 113, 114, 115)]
         n_created = c1[3] - c0[3]
@@ -217,7 +245,7 @@ def measure(capi, device, steps, warmup, mode, pool_mb, fanout=None, barrier=Non
                 "window_GiB": pool.size / GiB, "burst": burst,
                 "backend_in_effect": {0: "hip", 2: "hybrid", 3: "drm"}.get(int(capi.get_option(108)), "?"),
                 "kfd_create": int(capi.get_option(110)), "kfd_tlb_flush": int(capi.get_option(118)), "prt": int(capi.get_option(128)),
-                "max_extent_pages": int(capi.get_option(119)), "create_split": create_split}
+                "max_extent_pages": int(capi.get_option(119)), "create_split": create_split, "probe": probed}
     finally:
         pool.close()
 
@@ -242,6 +270,49 @@ def summarize(res, steps, n_gpus=1):
         "host_us_per_call": {k: round(v / 1e3 / steps, 1) for k, v in st.get("host_segments_ns", {}).items() if v},
     }
     return out
+
+
+SAMPLE_BYTES = 4096   # read per page of the last step: 1024 pages x 4 KiB, 16 MiB per float32 array
+
+
+def sample_last_step(pool, offsets, device_memory=True):
+    """What the caller of the last timed map call was handed, for --dump-outputs: per page of the batch (call order) SAMPLE_BYTES
+    at a seeded place, read through the mapping (a freshly backed page reads as zeros), then a seeded pattern written through
+    the mapping and read back (memory that is not backed, a PRT mapping, would drop the write and return zeros again).
+    hipMemcpy of the runtime torch has loaded, which the library registers every slot with; the unmap scrubs the pattern."""
+    import ctypes
+    import numpy as np
+    out = {"offsets": np.asarray(offsets, dtype=np.float64)}
+    if not device_memory:   # the rehearsal's cpu device keeps the books and maps nothing: no bytes to read
+        return out
+    base, nbytes = pool.tensors[0]
+    rng = np.random.default_rng(0)
+    where = rng.integers(0, pool.slot // SAMPLE_BYTES, len(offsets)) * SAMPLE_BYTES
+    pattern = rng.integers(0, 256, (len(offsets), SAMPLE_BYTES), dtype=np.uint8)
+    got, back = np.empty_like(pattern), np.empty_like(pattern)
+    hip = ctypes.CDLL("libamdhip64.so")
+
+    def copy(dst, src, kind):   # kind 1: host to device, 2: device to host
+        rc = hip.hipMemcpy(ctypes.c_void_p(dst), ctypes.c_void_p(src), ctypes.c_size_t(SAMPLE_BYTES), kind)
+        assert rc == 0, f"hipMemcpy (kind {kind}) on a page of the last step failed: {rc}"
+
+    for j, (o, w) in enumerate(zip(offsets, where)):
+        assert 0 <= o and o + pool.slot <= nbytes, (o, nbytes)
+        va = base + o + int(w)
+        copy(got[j].ctypes.data, va, 2)
+        copy(va, pattern[j].ctypes.data, 1)
+        copy(back[j].ctypes.data, va, 2)
+    out["kv_after_map"] = got.astype(np.float32)
+    out["kv_readback"] = back.astype(np.float32)
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def roofline_from(st):
@@ -466,18 +537,23 @@ ref.shutdown_kvcached()
 """
 
 
+REF_MAX_STEPS, REF_MAX_WARMUP = 24, 5   # the reference's step takes ~0.3 s (1024 x hipMemCreate + hipMemMap ...): a bounded sample
+
+
 def reference_on_box(steps, warmup, burst=False):
     """The REAL reference (oracle/_ref/vmm_ops.so, compiled from its own sources in the build
-    container) running its own HIP path on this GPU on the SAME workload (same window, warm-up, steps and
-    offsets): its FTensor::map per page = unmap zero alias + hipMemCreate + hipMemMap + hipMemSetAccess,
+    container) running its own HIP path on this GPU on the SAME workload (same window, warm-up and
+    offsets; at most REF_MAX_STEPS steps after at most REF_MAX_WARMUP, whatever --steps says - its line
+    reports the counts it ran): its FTensor::map per page = unmap zero alias + hipMemCreate + hipMemMap + hipMemSetAccess,
     no zero fill, no TLB invalidation (so its pages are not even reliably private).
     Context only."""
     so = os.path.join(REPO, "oracle", "_ref", "vmm_ops.so")
     if not os.path.exists(so):
         return None
+    steps, warmup = min(steps, REF_MAX_STEPS), min(warmup, REF_MAX_WARMUP)
     try:
         out = subprocess.run([sys.executable, "-c", REF_SNIPPET, so, str(steps), str(warmup), "burst" if burst else "cycle"],
-                             capture_output=True, text=True, timeout=600)
+                             capture_output=True, text=True, timeout=180)
         line = [l for l in out.stdout.splitlines() if l.startswith("{")]
         if out.returncode != 0 or not line:
             return {"error": (out.stderr or out.stdout)[-300:]}
@@ -803,7 +879,7 @@ def main():
     # VRAM the kernel has not handed out since boot is cleared inside the allocation (~80 us per 2 MiB), memory that was
     # wiped on release is not: the same burst later in this run (variants) shows the other side. DESIGN.md §4.5.
     first_touch = None
-    if world == 1 and not rehearsal and not args.no_variants and not use_dist_requested():
+    if args.full and world == 1 and not rehearsal and not args.no_variants and not use_dist_requested():
         try:
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--growth-burst-only", "--backend", args.backend, "--mode", args.mode],
                                  capture_output=True, text=True, timeout=300)
@@ -833,7 +909,13 @@ def main():
         fanout = CollectiveFanout(device=device if backend == "nccl" else "cpu", deferred_status=True)
         barrier = dist.barrier
 
-    res = measure(capi, device, args.steps, args.warmup, args.mode, args.pool_mb, fanout, barrier, sync, backend=args.backend)
+    probe = None
+    if args.dump_outputs:   # rank 0 reads its pages; the other ranks only wait for it (the barrier inside measure)
+        probe = (lambda pool, offs: sample_last_step(pool, offs, device_memory=not rehearsal)) if rank == 0 else (lambda pool, offs: None)
+    res = measure(capi, device, args.steps, args.warmup, args.mode, args.pool_mb, fanout, barrier, sync, backend=args.backend,
+                  probe=probe)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, res["probe"])
     elapsed = res["elapsed"]
     if use_dist:
         import torch.distributed as dist
@@ -850,7 +932,7 @@ def main():
         assert all(p == pages_by_rank[0] for p in pages_by_rank), f"ranks backed different amounts: {pages_by_rank}"
     main_sum = summarize(res, args.steps, world)
     shared = None
-    if use_dist and world > 1 and os.environ.get("KVC_BENCH_SHARED_POOL", "1") != "0":
+    if args.full and use_dist and world > 1 and os.environ.get("KVC_BENCH_SHARED_POOL", "1") != "0":
         import torch.distributed as dist
         dist.barrier()                       # every rank is past its timed region and has shut its allocator down
         shared = shared_pool_in_children(rank, world)
@@ -902,7 +984,7 @@ def main():
                 leg = (shared.get("page_ids_as_units") or {}).get(f"{k}_page_ids")
                 if isinstance(leg, dict):
                     line["config"][f"shared_pool_{k}_page_ids_ms"] = leg["export_ship_import_map_ms_p50_slowest_rank"]
-        if world == 1 and not rehearsal:
+        if args.full and world == 1 and not rehearsal:
             if first_touch is not None:
                 line["growth_burst_first_touch"] = first_touch
                 line["config"]["growth_burst_first_touch_GBps"] = first_touch.get("GBps")

@@ -8,6 +8,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -20,7 +23,7 @@ def _run(extra_env, *argv, timeout=300):
 
 
 def test_gpus_2_spawns_two_ranks_and_prints_one_line():
-    out = _run({}, "--gpus", "2", "--steps", "3", "--warmup", "1")
+    out = _run({}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full")
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -47,6 +50,43 @@ def test_gpus_2_spawns_two_ranks_and_prints_one_line():
             assert leg["export_ship_import_map_ms_p50_slowest_rank"] > 0
     assert line["config"]["shared_pool_8_page_ids_ms"] == sp["page_ids_as_units"]["8_page_ids"]["export_ship_import_map_ms_p50_slowest_rank"]
     assert line["rccl_world_size"] == 2
+
+
+def test_a_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs of its own (the shared-pool leg is a --full leg);
+    --dump-outputs writes what the last timed step handed its caller - on the cpu device, which maps nothing, its offsets."""
+    out = _run({}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["ranks"] == [0, 1]
+    assert not {"shared_pool", "variants", "cpu_baseline", "growth_burst_first_touch"} & set(line)
+    assert sorted(os.listdir(tmp_path)) == ["offsets.npy"]
+    offs = np.load(tmp_path / "offsets.npy")
+    assert offs.dtype == np.float64 and offs.shape == (1024,)
+    # the 3rd timed step after 1 warm-up step backs batch 3 of the window: its 1024 slots of 2 MiB, shuffled
+    assert sorted(int(o) for o in offs) == [(3 * 1024 + p) * (2 << 20) for p in range(1024)]
+    assert offs.astype(np.int64).tolist() != sorted(offs.astype(np.int64).tolist())
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_pages_of_the_last_step(tmp_path):
+    """On the GPU: the bytes read through the last step's mapping are zeros, and a pattern written through it reads back (a PRT
+    mapping would drop it); float32, within 64 MB."""
+    env = {k: v for k, v in os.environ.items() if k not in ("KVC_BENCH_REHEARSAL", "WORLD_SIZE", "RANK")}
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["value"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["kv_after_map.npy", "kv_readback.npy", "offsets.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
+    offs, after, back = (np.load(tmp_path / f"{n}.npy") for n in ("offsets", "kv_after_map", "kv_readback"))
+    assert sorted(int(o) for o in offs) == [(3 * 1024 + p) * (2 << 20) for p in range(1024)]
+    assert after.dtype == np.float32 and after.shape == (1024, 4096) and not after.any()
+    rng = np.random.default_rng(0)                   # bench.sample_last_step's seeded places, then its pattern
+    rng.integers(0, (2 << 20) // 4096, 1024)
+    want = rng.integers(0, 256, (1024, 4096), dtype=np.uint8)
+    assert back.dtype == np.float32 and np.array_equal(back, want.astype(np.float32))
 
 
 def test_under_a_launcher_it_does_not_spawn_again():

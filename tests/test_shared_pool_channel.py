@@ -4,6 +4,7 @@ stand-ins for the library's export / import (the real ones need a GPU: tests/tes
 gets exactly the descriptors rank 0 exported, in order, for exactly the offsets rank 0 named; a failure on ANY rank - the
 exporter's or one importer's - is an exception on EVERY rank, and the channel is usable afterwards (nothing is left unread)."""
 import os
+import resource
 import socket
 import sys
 
@@ -14,6 +15,13 @@ import kvc_testlib as T
 
 def _rank(rank, world, port, ipc, q):
     try:
+        # Descriptors in flight over unix sockets count against the sender's RLIMIT_NOFILE, summed over the user's processes
+        # (sendmsg fails with ETOOMANYREFS beyond it, unless privileged): the last round ships 800 to each of two peers, more
+        # than the usual soft limit of 1024.
+        soft, hard = resource.getrlimit(resource.RLIMIT_NOFILE)
+        want = 4096 if hard == resource.RLIM_INFINITY else min(4096, hard)
+        if soft != resource.RLIM_INFINITY and soft < want:
+            resource.setrlimit(resource.RLIMIT_NOFILE, (want, hard))
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), KVCACHED_LOG_LEVEL="ERROR", KVCACHED_IPC_NAME=ipc)
         sys.path.insert(0, T.REPO)
         import torch.distributed as dist

@@ -6,6 +6,7 @@ set -o pipefail
 export TMPDIR=/tmp
 STAGE=${1:-1}; R=${2:-r03}
 mkdir -p gpurun_out
+OUT=$_   # the folder just made (mkdir's last argument): the logs of this session go there
 if [ "$STAGE" = "1" ] || [ "$STAGE" = "tests" ]; then
   echo "== pytest -m gpu"
   timeout -k 10 1000 python -u -m pytest tests -m gpu -q --timeout=300 > gpurun_out/pytest_gpu.log 2>&1; rc=$?
@@ -16,8 +17,8 @@ if [ "$STAGE" = "1" ] || [ "$STAGE" = "tests" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; rc=$?
   tail -1 gpurun_out/smoke.log | cut -c1-300; echo "smoke rc=$rc"
   [ $rc -ne 0 ] && exit $rc
-  echo "== bench (the driver's command)"
-  timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench.log 2> gpurun_out/bench.err; rc=$?
+  echo "== bench --full (the driver's command with every leg: variants, cpu_baseline, ... - what tools_collect_profiles.py keeps)"
+  timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench.log" 2> "$OUT/bench.err"; rc=$?
   tail -1 gpurun_out/bench.log | cut -c1-1200; grep -v amdgpu.ids gpurun_out/bench.err | tail -5; echo "bench rc=$rc"
   [ $rc -ne 0 ] && exit $rc
   echo "== rocprofv3 kernel trace (same command, context legs off)"
