@@ -257,6 +257,20 @@ int kvc_zero_fill_pages(void *const *page_ptrs, size_t n, size_t page_bytes, voi
 int kvc_compact_blocks(void *const *region_bases, size_t n_regions, const int64_t *src_blocks,
                        const int64_t *dst_blocks, size_t n_moves, size_t block_bytes, void *stream, int sync);
 
+/* copy_blocks_to_host / copy_blocks_from_host: offload and restore of live blocks. For every block i < n and every
+ * region r < R of the group (kvc_get_region_bases order; R = 1 in the contiguous layout) copy block_bytes between
+ * region_base[r] + block_ids[i]*block_bytes and host + (i*R + r)*block_bytes: the host image is block-major,
+ * [block][region][bytes], n*R*block_bytes in all. `host` must be pinned host memory (hipHostMalloc / registered), 16-byte
+ * aligned, with room for the image. KVC_E_INVALID, with nothing launched, for: block_bytes zero or not a multiple of 16, a
+ * negative id or one outside the tensors, a duplicate id in from_host (the writes would race), pageable or misaligned
+ * `host`, or a (block, region) byte range that touches a slot which is not backed by a page (checked under the
+ * allocator's lock). KVC_E_NO_GPU on the "cpu" device. Ordered on `stream` like the other kernels; the caller keeps the
+ * blocks allocated and the host buffer alive until the copy is over (sync, or an event behind it). */
+int kvc_copy_blocks_to_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, void *host,
+                            void *stream, int sync);
+int kvc_copy_blocks_from_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, const void *host,
+                              void *stream, int sync);
+
 /* Region bases of a group's KV tensors in map order (layer-major, K then V), for compact_blocks.
  * Returns the count; copies if cap suffices. */
 int64_t kvc_get_region_bases(int64_t group_id, void **out, int64_t cap);

@@ -129,6 +129,8 @@ SIGNATURES = {
     "kvc_zero_fill_pages": (_int, [_VPP, _sz, _sz, _vp, _int]),
     "kvc_compact_blocks": (_int, [_VPP, _sz, _I64P, _I64P, _sz, _sz, _vp, _int]),
     "kvc_get_region_bases": (_i64, [_i64, _VPP, _i64]),
+    "kvc_copy_blocks_to_host": (_int, [_i64, _I64P, _sz, _sz, _vp, _vp, _int]),
+    "kvc_copy_blocks_from_host": (_int, [_i64, _I64P, _sz, _sz, _vp, _vp, _int]),
     "kvc_expand_block_ids": (_int, [_I64P, _sz, _i64, _vp, _vp]),
     "kvc_alloc_extend_indices": (_int, [_vp, _vp, _vp, _sz, _I64P, _sz, _i64, _vp, _sz, _vp]),
     "kvc_alloc_decode_indices": (_int, [_vp, _vp, _sz, _I64P, _sz, _i64, _vp, _vp]),
@@ -265,6 +267,20 @@ def compact_blocks(region_bases: Sequence[int], src_blocks: Sequence[int], dst_b
         raise ValueError("src_blocks and dst_blocks differ in length")
     check(lib.kvc_compact_blocks(ptr_array(region_bases), len(region_bases), i64_array(src_blocks),
                                  i64_array(dst_blocks), len(src_blocks), block_bytes, stream or None, int(sync)))
+
+
+def copy_blocks_to_host(group_id: int, block_ids: Sequence[int], block_bytes: int, host_ptr: int, stream: int = 0,
+                        sync: bool = True) -> None:
+    """Every region's copy of blocks `block_ids` -> the block-major image at host_ptr (pinned memory; HIP kernel)."""
+    check(lib.kvc_copy_blocks_to_host(group_id, i64_array(block_ids), len(block_ids), block_bytes, host_ptr or None,
+                                      stream or None, int(sync)))
+
+
+def copy_blocks_from_host(group_id: int, block_ids: Sequence[int], block_bytes: int, host_ptr: int, stream: int = 0,
+                          sync: bool = True) -> None:
+    """The block-major image at host_ptr (pinned memory) -> every region's copy of blocks `block_ids` (HIP kernel)."""
+    check(lib.kvc_copy_blocks_from_host(group_id, i64_array(block_ids), len(block_ids), block_bytes, host_ptr or None,
+                                        stream or None, int(sync)))
 
 
 def get_region_bases(group_id: int = 0) -> List[int]:

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 #include "kernels.hpp"
 #include "kv_allocator.hpp"
@@ -466,6 +467,52 @@ int kvc_compact_blocks(void *const *region_bases, size_t n_regions, const int64_
     if (sync) ctx->sync(static_cast<hipStream_t>(stream));
     return KVC_OK;
   });
+}
+
+namespace {
+// Host side of kvc_copy_blocks_{to,from}_host: arguments, the host buffer (pinned, 16-byte aligned, resolved to the address
+// the GPU reaches it at), then the allocator's own checks and the launch.
+int copy_blocks_host(bool to_host, int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, const void *host,
+                     void *stream, int sync) {
+  return guarded([&]() -> int {
+    GpuContext *ctx = KvAllocator::gpu();
+    if (!ctx) throw NoGpuError("copying blocks to or from host memory needs init_kvcached on a GPU device");
+    if (n && (!block_ids || !host)) throw InvalidError("NULL argument");
+    if (block_bytes == 0 || block_bytes % 16 != 0) throw InvalidError("block_bytes must be a positive multiple of 16");
+    for (size_t i = 0; i < n; ++i)
+      if (block_ids[i] < 0) throw InvalidError("negative block id");
+    if (!to_host && n > 1) { // two copies into one block would race
+      std::vector<int64_t> sorted(block_ids, block_ids + n);
+      std::sort(sorted.begin(), sorted.end());
+      if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw InvalidError("duplicate block id");
+    }
+    if (n == 0) return KVC_OK;
+    if (reinterpret_cast<uintptr_t>(host) % 16 != 0) throw InvalidError("host buffer is not 16-byte aligned");
+    ctx->bind();
+    hipPointerAttribute_t attr;
+    std::memset(&attr, 0, sizeof(attr));
+    if (hipPointerGetAttributes(&attr, host) != hipSuccess || attr.type != hipMemoryTypeHost || !attr.devicePointer) {
+      (void)hipGetLastError();
+      throw InvalidError("host buffer is not pinned host memory");
+    }
+    char *dev = static_cast<char *>(attr.devicePointer);
+    if (attr.hostPointer) dev += static_cast<const char *>(host) - static_cast<const char *>(attr.hostPointer);
+    if (reinterpret_cast<uintptr_t>(dev) % 16 != 0) throw InvalidError("host buffer is not 16-byte aligned on the device side");
+    KvAllocator::global(group_id)->copy_blocks_host(to_host, block_ids, n, block_bytes, dev, static_cast<hipStream_t>(stream));
+    if (sync) ctx->sync(static_cast<hipStream_t>(stream));
+    return KVC_OK;
+  });
+}
+} // namespace
+
+int kvc_copy_blocks_to_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, void *host, void *stream,
+                            int sync) {
+  return copy_blocks_host(true, group_id, block_ids, n, block_bytes, host, stream, sync);
+}
+
+int kvc_copy_blocks_from_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, const void *host,
+                              void *stream, int sync) {
+  return copy_blocks_host(false, group_id, block_ids, n, block_bytes, host, stream, sync);
 }
 
 int64_t kvc_get_region_bases(int64_t group_id, void **out, int64_t cap) {

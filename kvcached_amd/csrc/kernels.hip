@@ -396,4 +396,127 @@ hipError_t launch_compact_blocks(void *const *bases, int n_regions, const int64_
   return hipGetLastError();
 }
 
+
+// ---------------------------------------------------------------------------- copy_blocks_to_host / copy_blocks_from_host
+// Offload / restore of live blocks (KVCacheManager.offload / .restore): for block i < n and region r < n_regions,
+//   host + ((i * row_regions + region0 + r) * block_bytes)  <->  base[r] + id[i] * block_bytes
+// The host image is block-major ([block][region][bytes]); `host` is the device address of pinned host memory.
+// The far side is the host link (PCIe Gen5 x16, 63 GB/s by spec, against 6+ TB/s of HBM), so what matters is only that
+// enough requests are in flight to cover its latency - microseconds for a read of host memory: one workgroup per
+// <= 16 KiB tile of a (block, region) pair, every lane with all four of its 16-byte loads issued before its first store.
+// That is 16 KiB in flight per workgroup and up to 8 workgroups per CU, where 63 GB/s x 2 us of latency is 126 KiB for
+// the whole chip. No LDS, no grid-stride loop, the tables in the kernarg segment as in compact_blocks. The HBM side
+// is accessed non-temporally (every byte once); the host side with plain accesses. Workgroups are ordered tile-fastest,
+// then region, then block, so consecutive workgroups cover consecutive host bytes.
+struct HostCopyArgs {
+  void *base[kMaxRegionsPerLaunch];
+  int64_t id[kMaxIdsPerLaunch];
+};
+static_assert(sizeof(HostCopyArgs) <= 12 * 1024, "kernarg segment budget");
+
+static constexpr int kHostCopyThreads = 256; // 4 waves
+static constexpr int kHostCopyWaves = kHostCopyThreads / 64;
+static constexpr int kHostCopyTile = 16 * 1024; // bytes per workgroup
+static constexpr int kHostCopyPieces = kHostCopyTile / kPiece / kHostCopyWaves; // 1 KiB wave-instructions per wave
+
+template <bool TO_HOST>
+__device__ __forceinline__ void copy_blocks_host_body(const HostCopyArgs &a, char *host, unsigned n_regions, unsigned region0,
+                                                      unsigned row_regions, unsigned tiles, unsigned block_bytes) {
+  const unsigned pair = blockIdx.x / tiles, t = blockIdx.x - pair * tiles;
+  const unsigned i = pair / n_regions, r = pair - i * n_regions;
+  char *dev = static_cast<char *>(a.base[r]) + a.id[i] * (int64_t)block_bytes + (size_t)t * kHostCopyTile;
+  char *hst = host + ((size_t)i * row_regions + region0 + r) * block_bytes + (size_t)t * kHostCopyTile;
+  const char *src = TO_HOST ? dev : hst;
+  char *dst = TO_HOST ? hst : dev;
+  const unsigned remain = block_bytes - t * kHostCopyTile; // bytes of this tile that exist (>= 16)
+  const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (remain >= (unsigned)kHostCopyTile) { // wave-uniform: every tile but a ragged last one
+    v4u v[kHostCopyPieces];
+#pragma unroll
+    for (int k = 0; k < kHostCopyPieces; ++k) {
+      const v4u *in = reinterpret_cast<const v4u *>(src + (k * kHostCopyWaves + wave) * kPiece + lane * 16);
+      v[k] = TO_HOST ? __builtin_nontemporal_load(in) : *in;
+    }
+#pragma unroll
+    for (int k = 0; k < kHostCopyPieces; ++k) {
+      v4u *o = reinterpret_cast<v4u *>(dst + (k * kHostCopyWaves + wave) * kPiece + lane * 16);
+      if (TO_HOST)
+        *o = v[k];
+      else
+        __builtin_nontemporal_store(v[k], o);
+    }
+  } else {
+    v4u v[kHostCopyPieces];
+#pragma unroll
+    for (int k = 0; k < kHostCopyPieces; ++k) {
+      const unsigned off = (k * kHostCopyWaves + wave) * kPiece + lane * 16;
+      if (off < remain) {
+        const v4u *in = reinterpret_cast<const v4u *>(src + off);
+        v[k] = TO_HOST ? __builtin_nontemporal_load(in) : *in;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kHostCopyPieces; ++k) {
+      const unsigned off = (k * kHostCopyWaves + wave) * kPiece + lane * 16;
+      if (off < remain) {
+        v4u *o = reinterpret_cast<v4u *>(dst + off);
+        if (TO_HOST)
+          *o = v[k];
+        else
+          __builtin_nontemporal_store(v[k], o);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kHostCopyThreads) void copy_blocks_to_host_kernel(HostCopyArgs a, char *host, unsigned n_regions,
+                                                                                unsigned region0, unsigned row_regions,
+                                                                                unsigned tiles, unsigned block_bytes) {
+  copy_blocks_host_body<true>(a, host, n_regions, region0, row_regions, tiles, block_bytes);
+}
+
+__global__ __launch_bounds__(kHostCopyThreads) void copy_blocks_from_host_kernel(HostCopyArgs a, char *host, unsigned n_regions,
+                                                                                  unsigned region0, unsigned row_regions,
+                                                                                  unsigned tiles, unsigned block_bytes) {
+  copy_blocks_host_body<false>(a, host, n_regions, region0, row_regions, tiles, block_bytes);
+}
+
+static hipError_t launch_copy_blocks_host(bool to_host, void *const *bases, int n_regions, int region0, int row_regions,
+                                          const int64_t *ids, int n, size_t block_bytes, void *host, hipStream_t stream) {
+  if (n_regions <= 0 || n <= 0) return hipSuccess;
+  if (n_regions > kMaxRegionsPerLaunch || n > kMaxIdsPerLaunch || region0 < 0 || row_regions < region0 + n_regions ||
+      block_bytes == 0 || block_bytes % 16 != 0 || block_bytes > 0x7fffffffull || reinterpret_cast<uintptr_t>(host) % 16 != 0)
+    return hipErrorInvalidValue;
+  HostCopyArgs a;
+  for (int r = 0; r < n_regions; ++r) {
+    if (reinterpret_cast<uintptr_t>(bases[r]) % 16 != 0) return hipErrorInvalidValue;
+    a.base[r] = bases[r];
+  }
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0) return hipErrorInvalidValue;
+    a.id[i] = ids[i];
+  }
+  const unsigned tiles = (unsigned)((block_bytes + kHostCopyTile - 1) / kHostCopyTile);
+  const size_t grid = (size_t)tiles * (size_t)n * (size_t)n_regions;
+  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+  const unsigned nr = (unsigned)n_regions, r0 = (unsigned)region0, rr = (unsigned)row_regions, bb = (unsigned)block_bytes;
+  char *h = static_cast<char *>(host);
+  if (to_host)
+    copy_blocks_to_host_kernel<<<dim3((unsigned)grid), dim3(kHostCopyThreads), 0, stream>>>(a, h, nr, r0, rr, tiles, bb);
+  else
+    copy_blocks_from_host_kernel<<<dim3((unsigned)grid), dim3(kHostCopyThreads), 0, stream>>>(a, h, nr, r0, rr, tiles, bb);
+  return hipGetLastError();
+}
+
+hipError_t launch_copy_blocks_to_host(void *const *bases, int n_regions, int region0, int row_regions, const int64_t *ids, int n,
+                                      size_t block_bytes, void *host, hipStream_t stream) {
+  return launch_copy_blocks_host(true, bases, n_regions, region0, row_regions, ids, n, block_bytes, host, stream);
+}
+
+hipError_t launch_copy_blocks_from_host(void *const *bases, int n_regions, int region0, int row_regions, const int64_t *ids,
+                                        int n, size_t block_bytes, const void *host, hipStream_t stream) {
+  return launch_copy_blocks_host(false, bases, n_regions, region0, row_regions, ids, n, block_bytes, const_cast<void *>(host),
+                                 stream);
+}
+
 } // namespace kvc

@@ -30,6 +30,15 @@ hipError_t launch_zero_fill_pages(void *const *pages, int n, size_t page_bytes, 
 hipError_t launch_compact_blocks(void *const *bases, int n_regions, const int64_t *src, const int64_t *dst, int n_moves,
                                  size_t block_bytes, hipStream_t stream, int variant = 0);
 
+// Copy blocks between the regions and a block-major host image: for i < n, r < n_regions,
+//   host + ((i * row_regions + region0 + r) * block_bytes)  <->  bases[r] + ids[i]*block_bytes
+// `host` is the device address of pinned host memory, 16-byte aligned; n <= kMaxIdsPerLaunch, n_regions <= kMaxRegionsPerLaunch
+// (the caller splits larger requests; region0 / row_regions place a slice of the regions inside a row of the image).
+hipError_t launch_copy_blocks_to_host(void *const *bases, int n_regions, int region0, int row_regions, const int64_t *ids, int n,
+                                      size_t block_bytes, void *host, hipStream_t stream);
+hipError_t launch_copy_blocks_from_host(void *const *bases, int n_regions, int region0, int row_regions, const int64_t *ids,
+                                        int n, size_t block_bytes, const void *host, hipStream_t stream);
+
 // One lane: optionally store `value` to *p, then copy *p to *out_dev (the TLB self test's view of memory).
 hipError_t launch_peek_poke(void *p, unsigned *out_dev, unsigned value, bool do_write, hipStream_t stream);
 

@@ -1027,6 +1027,45 @@ std::vector<void *> KvAllocator::region_bases() {
   return b;
 }
 
+void KvAllocator::copy_blocks_host(bool to_host, const int64_t *ids, size_t n, size_t block_bytes, void *host, hipStream_t s) {
+  if (!ctx_) throw NoGpuError("copying blocks to or from host memory needs init_kvcached on a GPU device");
+  std::unique_lock<std::mutex> g(mu_, std::defer_lock);
+  lock_foreground(g);
+  if (layers_.empty()) throw InvalidError("KV tensors are not created");
+  // the regions in region_bases() order: (region, offset of the base inside it, bytes from the base to the end of its half)
+  struct Span {
+    KvRegion *r;
+    size_t off, bytes;
+  };
+  std::vector<Span> spans;
+  std::vector<void *> bases;
+  const bool halves = !contiguous_ && !unified_pool_ && num_kv_buffers_ == 2;
+  for (auto &r : layers_) {
+    spans.push_back({r.get(), 0, halves ? r->size / 2 : r->size});
+    if (halves) spans.push_back({r.get(), r->size / 2, r->size / 2});
+  }
+  for (auto &sp : spans) bases.push_back(sp.r->base + sp.off);
+  // Every slot that a (block, region) byte range touches must be backed by a page - a block may straddle two slots. An
+  // unbacked slot is unmapped VA in the lazy mode (a GPU fault) and a PRT entry in the default one, which the TLBs would
+  // cache. The page-table entries of a backed slot stay valid whatever is mapped or unmapped around it
+  // (DESIGN.md §4.14), so the launch needs no fence beyond this lock.
+  for (auto &sp : spans) {
+    const size_t ps = sp.r->page_size;
+    for (size_t i = 0; i < n; ++i) {
+      if (ids[i] < 0 || (size_t)ids[i] >= sp.bytes / block_bytes)
+        throw InvalidError("block id " + std::to_string(ids[i]) + " is outside the KV tensors");
+      const size_t first = sp.off + (size_t)ids[i] * block_bytes, last = first + block_bytes - 1;
+      for (size_t slot = first / ps; slot <= last / ps; ++slot) {
+        const uint8_t st = sp.r->mapped[slot];
+        if (st != 1 && st != 2 && st != 4 && st != 5)
+          throw InvalidError("block id " + std::to_string(ids[i]) + " lies on a slot of " + sp.r->name + " that is not backed");
+      }
+    }
+  }
+  ctx_->bind();
+  ctx_->copy_blocks_host(to_host, bases.data(), bases.size(), ids, n, block_bytes, host, s);
+}
+
 // Offsets -> (region, slot) in the reference's order: layer-major, then offset, K before V
 // (allocator.cpp:168-207). Contiguous: one compound slot per offset. Unified pool: one slot per layer.
 std::vector<KvAllocator::Slot> KvAllocator::slots_for(const offset_t *offsets, size_t n) {

@@ -118,6 +118,9 @@ public:
   void zero_fill(void *const *pages, size_t n, size_t page_bytes, hipStream_t s);
   void compact(void *const *bases, size_t n_regions, const int64_t *src, const int64_t *dst, size_t n_moves,
                size_t block_bytes, hipStream_t s);
+  // blocks <-> a block-major host image (copy_blocks_to_host / _from_host); `host` is a device address of pinned memory
+  void copy_blocks_host(bool to_host, void *const *bases, size_t n_regions, const int64_t *ids, size_t n, size_t block_bytes,
+                        void *host, hipStream_t s);
   void sync(hipStream_t s); // hipStreamSynchronize + harvest event timings
   // ---- zeroing pages on their way BACK (drm backend, extents with an alias mapping).
   // A page handed out by map_slots must read zero. Filling it there puts 0.3 us per page of GPU time between the
@@ -346,6 +349,10 @@ public:
   bool map_to_kv_tensors(const offset_t *offsets, size_t n);
   bool unmap_from_kv_tensors(const offset_t *offsets, size_t n);
   std::vector<void *> region_bases(); // layer-major, K then V (compact_blocks' region table)
+  // Offload / restore: copy blocks `ids` of every region (region_bases() order) to / from the block-major image at `host`
+  // (device address of pinned host memory). Under the lock, every slot a (block, region) byte range touches must be backed
+  // (states 1, 2, 4, 5), else InvalidError and nothing is launched; the launch is issued under the lock too.
+  void copy_blocks_host(bool to_host, const int64_t *ids, size_t n, size_t block_bytes, void *host, hipStream_t s);
   bool uses_prt();                    // unbacked slots of this group's regions are PRT mappings
   size_t lanes_per_extent();          // page ids are backed by lanes: lanes a buffer holds at most (0: per-slot pages)
 

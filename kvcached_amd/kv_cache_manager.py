@@ -16,7 +16,9 @@ Order-defining rules that the golden traces pin (reference line numbers):
   * a shrink that cannot complete is finished inside the free() that makes room    (:354-360)
 
 Additions (not in the reference, off unless called): `compact()` — plans and executes, with the
-compact_blocks HIP kernel, the block moves that empty sparsely used pages so they can be unmapped.
+compact_blocks HIP kernel, the block moves that empty sparsely used pages so they can be unmapped;
+`offload()` / `restore()` — copy live blocks to pinned host memory and free them, and later bring
+them back under new ids (copy_blocks_to_host / copy_blocks_from_host HIP kernels).
 """
 from __future__ import annotations
 
@@ -136,6 +138,8 @@ class KVCacheManager:
             remote = hook()
         if self.world_size > 1 or remote:
             self._install_broadcast_callbacks(remote)
+        # the KV tensors live in other processes: nothing here can copy their bytes (offload / restore refuse)
+        self._kv_remote = self.world_size > 1 or remote
 
         self.num_avail_blocks = 0  # free blocks inside avail_pages only
         self.avail_pages: Dict[int, InternalPage] = {}
@@ -472,11 +476,7 @@ class KVCacheManager:
         if not moves:
             return {}
         from kvcached_amd import capi
-        bases = capi.get_region_bases(self.group_id)
-        if CONTIGUOUS_LAYOUT:   # one region; a block of all layers and K/V is one contiguous run
-            block_bytes = self.block_mem_size * self.num_layers * self.num_kv_buffers
-        else:
-            block_bytes = self.block_mem_size
+        bases, block_bytes = self._block_geometry()
         src = [s for s, _ in moves]
         dst = [d for _, d in moves]
         capi.compact_blocks(bases, src, dst, block_bytes, sync=True)
@@ -490,3 +490,163 @@ class KVCacheManager:
             (self.full_pages if page.full() else self.avail_pages)[pid] = page
         self.free(src)
         return dict(moves)
+
+    def _block_geometry(self) -> Tuple[List[int], int]:
+        """(region bases, bytes of one block in one region) of this group's KV tensors. Contiguous layout: one region,
+        and a block of all layers and K/V is one contiguous run; otherwise one region per layer (and K/V half)."""
+        from kvcached_amd import capi
+        bases = capi.get_region_bases(self.group_id)
+        if CONTIGUOUS_LAYOUT:
+            return bases, self.block_mem_size * self.num_layers * self.num_kv_buffers
+        return bases, self.block_mem_size
+
+    def _geometry_key(self, n_regions: int, block_bytes: int) -> Tuple[int, bool, int, int]:
+        return (self.group_id, bool(CONTIGUOUS_LAYOUT), n_regions, block_bytes)
+
+    # ------------------------------------------------------------------ host offload (addition)
+    def _check_live_blocks(self, ids: List[int]) -> None:
+        """ValueError unless `ids` are distinct blocks that are allocated, not reserved and not the null block."""
+        if not ids:
+            raise ValueError("offload needs at least one block id")
+        if len(set(ids)) != len(ids):
+            raise ValueError("duplicate block id in offload")
+        if self.null_block is not None and self.null_block[0] in ids:
+            raise ValueError(f"block {self.null_block[0]} is the null block")
+        reserved = set(self.reserved_blocks).intersection(ids)
+        if reserved:
+            raise ValueError(f"blocks {sorted(reserved)} are reserved (try_to_reserve), not in use")
+        for b in ids:
+            if not 0 <= b < self.num_blocks:
+                raise ValueError(f"block id {b} is outside the pool of {self.num_blocks} blocks")
+        for pid, blocks in self.page_allocator.group_indices_by_page(ids, self.block_mem_size).items():
+            if pid in self.full_pages:
+                continue
+            page = self.avail_pages.get(pid)
+            free = set(page.get_free_blocks()) if page is not None else None
+            for b in blocks:
+                if free is None or b in free:
+                    raise ValueError(f"block {b} is free")
+
+    @synchronized
+    def offload(self, block_ids: List[int], out: Optional["torch.Tensor"] = None) -> "OffloadedBlocks":
+        """Copy live blocks to pinned host memory, wait until the bytes are there, and free the blocks.
+
+        The copy runs on torch.cuda.current_stream(), behind whatever the engine queued there. `out` (optional): a
+        pinned, contiguous uint8 tensor with room for len(block_ids) * n_regions * block_bytes bytes. Raises ValueError
+        (nothing changed) for an empty or duplicated id list, the null block, a free or a reserved block, or an unfit
+        `out`; RuntimeError when the KV tensors live in other processes (tensor parallelism, worker IPC)."""
+        self._wait_post_init()
+        if self._kv_remote:
+            raise RuntimeError("offload needs the KV tensors in this process (world_size == 1, no worker IPC); "
+                               "offload under tensor parallelism is not supported")
+        ids = [int(b) for b in block_ids]
+        self._check_live_blocks(ids)
+        import torch
+        from kvcached_amd import capi
+        bases, block_bytes = self._block_geometry()
+        nbytes = len(ids) * len(bases) * block_bytes
+        if out is None:
+            # pinned wherever a GPU exists; without one the library refuses the copy anyway (KVC_E_NO_GPU)
+            out = torch.empty(nbytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        elif (out.dtype != torch.uint8 or out.device.type != "cpu" or not out.is_contiguous() or out.numel() < nbytes
+              or not out.is_pinned()):
+            raise ValueError(f"out must be a pinned, contiguous uint8 CPU tensor of at least {nbytes} bytes")
+        data = out.view(-1)[:nbytes]
+        _on_current_stream(lambda s: capi.copy_blocks_to_host(self.group_id, ids, block_bytes, data.data_ptr(), s, sync=True))
+        self.free(ids)   # only now: free() may unmap pages, and the copy has read them
+        return OffloadedBlocks(ids, data, self._geometry_key(len(bases), block_bytes))
+
+    @synchronized
+    def restore(self, handle: "OffloadedBlocks") -> Optional[List[int]]:
+        """Allocate len(handle.block_ids) blocks and copy the offloaded bytes into them: new_ids[i] holds
+        handle.block_ids[i]. Returns None (nothing changed) when the pool cannot hold them. The copy is queued on
+        torch.cuda.current_stream() and not waited for: later work on that stream sees the data."""
+        self._wait_post_init()
+        if self._kv_remote:
+            raise RuntimeError("restore needs the KV tensors in this process (world_size == 1, no worker IPC)")
+        if handle.data is None:
+            raise ValueError("the offloaded blocks were released")
+        from kvcached_amd import capi
+        bases, block_bytes = self._block_geometry()
+        key = self._geometry_key(len(bases), block_bytes)
+        if handle.geometry != key:
+            raise ValueError(f"offloaded blocks of geometry {handle.geometry} (group, contiguous, regions, block bytes) "
+                             f"cannot be restored into {key}")
+        new_ids = self.alloc(len(handle.block_ids))
+        if new_ids is None:
+            return None
+        try:
+            _on_current_stream(lambda s: capi.copy_blocks_from_host(self.group_id, new_ids, block_bytes,
+                                                                    handle.data.data_ptr(), s, sync=False))
+        except Exception:
+            self.free(new_ids)
+            raise
+        handle._record()
+        return new_ids
+
+
+_side_streams: Dict[int, Any] = {}
+
+
+def _on_current_stream(launch) -> None:
+    """launch(hipStream_t), ordered on torch.cuda.current_stream(): behind the work queued there, and ahead of what is
+    queued after it. In the C ABI a NULL stream names the library's own stream, so work meant for the device's null
+    stream (torch's default one) goes through a side stream fenced to it on both ends. Without a GPU: launch(0), which
+    the library refuses itself."""
+    import torch
+    if not torch.cuda.is_available():
+        return launch(0)
+    cur = torch.cuda.current_stream()
+    if cur.cuda_stream:
+        return launch(cur.cuda_stream)
+    side = _side_streams.get(cur.device.index)
+    if side is None:
+        side = _side_streams[cur.device.index] = torch.cuda.Stream(device=cur.device)
+    side.wait_stream(cur)
+    try:
+        launch(side.cuda_stream)
+    finally:
+        cur.wait_stream(side)
+
+
+class OffloadedBlocks:
+    """What KVCacheManager.offload() returns: the bytes of offloaded blocks in pinned host memory.
+
+    block_ids: the ids the blocks had (restore()'s result is in the same order); data: the pinned uint8 image,
+    block-major ([block][region][block_bytes]); geometry: (group_id, contiguous layout, regions, block_bytes);
+    event: the event behind the latest restore() copy (None before the first). The pinned buffer is not given back -
+    by release() or by garbage collection - before every restore() copy from it has finished."""
+
+    def __init__(self, block_ids: List[int], data: "torch.Tensor", geometry: Tuple[int, bool, int, int]):
+        self.block_ids = list(block_ids)
+        self.data = data
+        self.geometry = geometry
+        self._events: List[Any] = []
+
+    @property
+    def event(self):
+        return self._events[-1] if self._events else None
+
+    def _record(self) -> None:
+        """An event behind the restore() copy just queued on the current stream."""
+        import torch
+        self._events = [e for e in self._events if not e.query()]
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        self._events.append(ev)
+
+    def release(self) -> None:
+        """Wait for the restore() copies still reading the buffer, then drop it."""
+        for ev in self._events:
+            ev.synchronize()
+        self._events = []
+        self.data = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return len(self.block_ids)
