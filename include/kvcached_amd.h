@@ -113,8 +113,9 @@ int kvc_unmap_from_kv_tensors(const int64_t *offsets, size_t n, int64_t group_id
  *                              pages are also allocated straight from KFD (AMDKFD_IOC_ALLOC_MEMORY_OF_GPU on the
  *                              library's own fd of /dev/kfd: 5 us flat instead of the runtime's O(live handles);
  *                              KVCACHED_DRM_KFD_CREATE=false keeps ROCr's creation; kvc_get_option(110) = 1 when active).
- *                              KVCACHED_PHYS_CHUNK_PAGES=k (default 1) allocates that memory in chunks of k pages and
- *                              maps runs of adjacent slots with one ioctl (opt-in).
+ *                              KVCACHED_PHYS_CHUNK_PAGES=k (default 1024, at most 1024; 1 = single pages) backs a run
+ *                              of up to k adjacent slots with one buffer of that many pages and maps it with one ioctl
+ *                              (run-sized extents; kvc_get_option(119) reports k).
  *                              DESIGN.md §4.6/§4.7.
  *   KVC_OPT_UNMAP_INVALIDATION_US  compat regions only (env KVCACHED_UNMAP_INVALIDATION_US). 0 (default): kvc_unmap_from_kv_tensors
  *                          invalidates the GPU TLBs before it returns - a freed address reads as zeros from that moment on.

@@ -42,19 +42,120 @@ using phys_handle_t = uint64_t; // hipMemGenericAllocationHandle_t (a pointer), 
 
 // A handle names ONE page-sized piece of an extent. For a one-page extent - every backend but drm, and single slots there -
 // the piece id IS the buffer handle, untouched (ROCr's handles use bits above 48: nothing is ever masked out of them).
-// A piece of a multi-page extent - those are KFD buffer handles, (gpu_id << 32 | idr) < 2^48 - is tagged with bit 63 and
-// carries the extent's size - 1 in bits 48-55 and the piece index in bits 56-62.
-constexpr int kPieceShift = 56, kPagesShift = 48;
+// A piece of a multi-page extent - those are KFD buffer handles, gpu_id << 32 | idr with a 16-bit gpu_id - is tagged with
+// bit 63 and carries the piece index in bits 53-62 and the extent's size - 1 in bits 43-52; the buffer handle itself is
+// packed into bits 0-42 (gpu_id in bits 27-42, idr in bits 0-26). A buffer whose handle does not pack (can_tag) is never
+// made into pieces: the pool gives it back and fails the call.
+constexpr int kPieceShift = 53, kPagesShift = 43, kIdrBits = 27;
 constexpr uint64_t kPieceTag = 1ull << 63;
-constexpr unsigned kMaxExtentPages = 64; // pieces of an extent are tracked in one 64-bit mask
+constexpr unsigned kMaxExtentPages = 1024; // 2 GiB of 2 MiB pages: one bench batch (10 bits each for size - 1 and index)
+constexpr uint64_t kIdrMask = (1ull << kIdrBits) - 1, kGpuIdMask = 0xffffull;
 inline bool is_piece(phys_handle_t h) { return (h & kPieceTag) != 0; }
+inline bool can_tag(phys_handle_t extent) { return (extent >> 48) == 0 && (extent & 0xffffffffull) <= kIdrMask; }
 inline phys_handle_t piece_id(phys_handle_t extent, unsigned piece, unsigned pages = 1) {
   if (pages <= 1) return extent;
-  return extent | kPieceTag | (static_cast<uint64_t>(pages - 1) << kPagesShift) | (static_cast<uint64_t>(piece) << kPieceShift);
+  const uint64_t packed = (((extent >> 32) & kGpuIdMask) << kIdrBits) | (extent & kIdrMask);
+  return packed | kPieceTag | (static_cast<uint64_t>(pages - 1) << kPagesShift) | (static_cast<uint64_t>(piece) << kPieceShift);
 }
-inline phys_handle_t chunk_of(phys_handle_t h) { return is_piece(h) ? (h & ((1ull << kPagesShift) - 1)) : h; }
-inline unsigned piece_of(phys_handle_t h) { return is_piece(h) ? static_cast<unsigned>((h >> kPieceShift) & 0x7f) : 0; }
-inline unsigned pages_of(phys_handle_t h) { return is_piece(h) ? static_cast<unsigned>((h >> kPagesShift) & 0xff) + 1 : 1; }
+inline phys_handle_t chunk_of(phys_handle_t h) {
+  return is_piece(h) ? (((h >> kIdrBits) & kGpuIdMask) << 32) | (h & kIdrMask) : h;
+}
+inline unsigned piece_of(phys_handle_t h) { return is_piece(h) ? static_cast<unsigned>((h >> kPieceShift) & 0x3ff) : 0; }
+inline unsigned pages_of(phys_handle_t h) { return is_piece(h) ? static_cast<unsigned>((h >> kPagesShift) & 0x3ff) + 1 : 1; }
+
+// The pieces of one extent as a set of bits: one word in place for up to 64 pieces, up to kMaxExtentPages / 64 on the
+// heap beyond. Operations between sets of different lengths treat the missing words as zero.
+class PieceMask {
+public:
+  PieceMask() = default;
+  explicit PieceMask(unsigned bits) : words_(words_for(bits)) {
+    if (words_ > 1) many_.assign(words_, 0);
+  }
+  static PieceMask full(unsigned n) {
+    PieceMask m(n);
+    uint64_t *w = m.w();
+    for (unsigned k = 0; k < m.words_; ++k) w[k] = n >= (k + 1) * 64 ? ~0ull : (n > k * 64 ? (1ull << (n - k * 64)) - 1 : 0);
+    return m;
+  }
+  unsigned words() const { return words_; }
+  bool test(unsigned i) const { return i < 64 * words_ && ((w()[i >> 6] >> (i & 63)) & 1); }
+  void set(unsigned i) { w()[i >> 6] |= 1ull << (i & 63); }   // (i < 64 * words())
+  void reset(unsigned i) { w()[i >> 6] &= ~(1ull << (i & 63)); }
+  PieceMask &operator|=(const PieceMask &o) {
+    for (unsigned k = 0; k < std::min(words_, o.words_); ++k) w()[k] |= o.w()[k];
+    return *this;
+  }
+  PieceMask &clear_from(const PieceMask &o) { // this &= ~o
+    for (unsigned k = 0; k < std::min(words_, o.words_); ++k) w()[k] &= ~o.w()[k];
+    return *this;
+  }
+  bool intersects(const PieceMask &o) const {
+    for (unsigned k = 0; k < std::min(words_, o.words_); ++k)
+      if (w()[k] & o.w()[k]) return true;
+    return false;
+  }
+  bool within(const PieceMask &o) const { // every bit of this is in o
+    for (unsigned k = 0; k < words_; ++k)
+      if (w()[k] & ~(k < o.words_ ? o.w()[k] : 0)) return false;
+    return true;
+  }
+  unsigned count() const {
+    unsigned c = 0;
+    for (unsigned k = 0; k < words_; ++k) c += (unsigned)__builtin_popcountll(w()[k]);
+    return c;
+  }
+  // lowest start of `want` consecutive set bits, or -1
+  int find_run(unsigned want) const {
+    int found = -1;
+    for_each_run([&](unsigned start, unsigned len) {
+      if (len < want) return false;
+      found = (int)start;
+      return true;
+    });
+    return found;
+  }
+  unsigned longest_run() const {
+    unsigned best = 0;
+    for_each_run([&](unsigned, unsigned len) {
+      best = std::max(best, len);
+      return false;
+    });
+    return best;
+  }
+
+private:
+  // f(start, length) for every maximal run of set bits in ascending order, and for a run that is still growing each time a
+  // word extends it (so that f can stop early: it returns true to stop)
+  template <class F> void for_each_run(F &&f) const {
+    unsigned len = 0, start = 0;
+    for (unsigned k = 0; k < words_; ++k) {
+      const uint64_t m = w()[k];
+      for (unsigned b = 0; b < 64;) {
+        const uint64_t rest = m >> b;
+        if (!rest) {
+          len = 0;
+          break;
+        }
+        const unsigned zeros = (unsigned)__builtin_ctzll(rest);
+        if (zeros) len = 0;
+        b += zeros;
+        const uint64_t inv = ~(m >> b);
+        const unsigned ones = inv ? std::min((unsigned)__builtin_ctzll(inv), 64 - b) : 64 - b;
+        if (!len) start = k * 64 + b;
+        len += ones;
+        if (f(start, len)) return;
+        b += ones;
+        if (b < 64) len = 0; // (a run that reaches bit 63 goes on in the next word)
+      }
+    }
+  }
+  static unsigned words_for(unsigned bits) { return bits > 64 ? (bits + 63) / 64 : 1; }
+  uint64_t *w() { return words_ == 1 ? &one_ : many_.data(); }
+  const uint64_t *w() const { return words_ == 1 ? &one_ : many_.data(); }
+  unsigned words_ = 1;
+  uint64_t one_ = 0;
+  std::vector<uint64_t> many_;
+};
 
 // Groups a batch of keys without sorting it (a batch of 1024 pages names a few dozen extents in any order): open addressing
 // over a table of indices into the list of groups, which keeps the order of first appearance.
@@ -149,7 +250,7 @@ public:
     want = std::min<size_t>(std::max<size_t>(want, 1), kmax_cfg_);
     std::unique_lock<std::mutex> lk(mu_);
     if (take_idle_locked((unsigned)want, (unsigned)want, out, recycled)) return want;
-    for (unsigned b = (unsigned)want; b <= kMaxExtentPages; ++b)
+    for (unsigned b = (unsigned)want; b <= kmax_cfg_; ++b)
       if (!by_run_[b].empty()) return take_free_run_locked(*by_run_[b].begin(), (unsigned)want, out, recycled);
     for (unsigned n = (unsigned)want + 1; n <= kmax_cfg_; ++n)
       if (take_idle_locked(n, (unsigned)want, out, recycled)) return want;
@@ -163,20 +264,20 @@ public:
     uint64_t tag = 0;
     const phys_handle_t h = drv_.create(n, &tag); // may throw: nothing of ours has changed yet
     lk.lock();
-    if (kmax_cfg_ > 1 && (h >> kPagesShift) != 0) { // cannot be told apart from a piece id: never happens with KFD handles
+    if (kmax_cfg_ > 1 && !can_tag(h)) { // its pieces could not be told apart from other handles: never happens with KFD handles
       lk.unlock();
       if (drv_.prepare_release) drv_.prepare_release(h, tag, n);
       (void)drv_.release(h);
-      throw std::runtime_error("extent pool: a multi-page buffer handle does not fit 48 bits");
+      throw std::runtime_error("extent pool: a multi-page buffer handle does not fit the piece encoding");
     }
     Extent &e = tracked_[h];
     e.seq = ++next_seq_;
-    e.n = (uint8_t)n;
-    e.free_mask = full_mask(n);
-    e.used_mask = 0;
+    e.n = (uint16_t)n;
+    e.free_mask = PieceMask::full(n);
+    e.used_mask = PieceMask(n);
     e.bucket = 0;
     e.tag = tag;
-    e.clean_mask = 0; // what the driver hands out is zero today, but that is not a documented guarantee
+    e.clean_mask = PieceMask(n); // what the driver hands out is zero today, but that is not a documented guarantee
     e.ticket = 0;
     free_pieces_ += n;
     held_pages_ += n;
@@ -216,27 +317,28 @@ public:
     const bool pressure = drv_.under_pressure && drv_.under_pressure();
     // pieces of one extent are handled together (one lookup, one re-bucketing): a batch lists a few dozen extents
     struct Group {
-      uint64_t bits = 0;
+      PieceMask bits;
       uint32_t cnt = 0;
       bool twice = false;
     };
     KeyGroups<Group> groups(n);
     for (size_t i = 0; i < n; ++i) {
       Group &g = groups.at(key_of(ps[i].h));
+      if (!g.cnt) g.bits = PieceMask(kmax_cfg_);
       const unsigned idx = idx_of(ps[i].h);
-      const uint64_t bit = idx < 64 ? 1ull << idx : 0;
-      g.twice = g.twice || bit == 0 || (g.bits & bit);
-      g.bits |= bit;
+      const bool fits = idx < 64 * g.bits.words();
+      g.twice = g.twice || !fits || g.bits.test(idx);
+      if (fits) g.bits.set(idx);
       ++g.cnt;
     }
     {
       std::lock_guard<std::mutex> g(mu_);
       for (auto &kv : groups.items()) {
         const phys_handle_t h = kv.first;
-        const uint64_t bits = kv.second.bits;
+        const PieceMask &bits = kv.second.bits;
         const size_t cnt = kv.second.cnt;
         auto it = tracked_.find(h);
-        if (it == tracked_.end() || kv.second.twice || (bits & it->second.free_mask) || (bits & ~full_mask(it->second.n))) {
+        if (it == tracked_.end() || kv.second.twice || bits.intersects(it->second.free_mask) || !bits.within(PieceMask::full(it->second.n))) {
           bad_releases_ += cnt; // pieces of an unknown extent, listed twice, or not out: never corrupt the masks
           continue;
         }
@@ -246,11 +348,11 @@ public:
           e.clean_mask |= bits;
           e.ticket = std::max(e.ticket, scrub_ticket);
         } else {
-          e.clean_mask &= ~bits;
+          e.clean_mask.clear_from(bits);
         }
         free_pieces_ += cnt;
         out_pieces_ -= cnt;
-        if (e.free_mask == full_mask(e.n)) { // the extent is whole again: idle, ours to reuse or to give back
+        if (e.free_mask.count() == e.n) { // the extent is whole again: idle, ours to reuse or to give back
           unbucket_locked(h, e);
           free_pieces_ -= e.n;
           idle_insert_locked(h, IdleInfo{e.seq, e.n, true, e.tag, e.clean_mask, e.ticket});
@@ -354,10 +456,15 @@ public:
       } catch (...) {
         break; // no memory: the reserve is a convenience
       }
+      if (kmax_cfg_ > 1 && !can_tag(h)) { // (see acquire_run: a multi-page pool takes every handle of its own apart)
+        if (drv_.prepare_release) drv_.prepare_release(h, tag, n);
+        (void)drv_.release(h);
+        break;
+      }
       std::lock_guard<std::mutex> g(mu_);
       held_pages_ += n;
       ctr_->created += n * scale_;
-      idle_insert_locked(h, IdleInfo{++next_seq_, (uint8_t)n, false, tag, 0, 0});
+      idle_insert_locked(h, IdleInfo{++next_seq_, (uint16_t)n, false, tag, PieceMask(n), 0});
       made += n;
     }
     return made;
@@ -382,32 +489,34 @@ public:
   Footprint footprint() {
     std::lock_guard<std::mutex> g(mu_);
     size_t partial = 0;
-    for (unsigned b = 1; b <= kMaxExtentPages; ++b) partial += by_run_[b].size();
+    for (unsigned b = 1; b <= kmax_cfg_; ++b) partial += by_run_[b].size();
     return Footprint{held_pages_, out_pieces_, idle_pages_, free_pieces_, partial, bad_releases_, kmax_cur_};
   }
   // how many pieces of this extent are handed out (0: unknown or whole)
   unsigned pieces_out(phys_handle_t extent) {
     std::lock_guard<std::mutex> g(mu_);
     auto it = tracked_.find(key_of(extent));
-    return it == tracked_.end() ? 0 : (unsigned)__builtin_popcountll(full_mask(it->second.n) & ~it->second.free_mask);
+    return it == tracked_.end() ? 0 : it->second.n - it->second.free_mask.count();
   }
 
 private:
   struct Extent {
     uint64_t seq = 0;
-    uint64_t free_mask = 0;
-    uint64_t used_mask = 0;  // pieces that have been handed out before (their memory may hold old data)
-    uint64_t clean_mask = 0; // free pieces that were queued for zeroing when they came back ...
-    uint64_t ticket = 0;     // ... by scrubs up to this number
-    uint64_t tag = 0;        // the driver's alias address of the buffer (0: none)
-    uint8_t n = 1;
-    uint8_t bucket = 0;      // longest free run (0: none free, not in by_run_)
+    PieceMask free_mask;
+    PieceMask used_mask;  // pieces that have been handed out before (their memory may hold old data)
+    PieceMask clean_mask; // free pieces that were queued for zeroing when they came back ...
+    uint64_t ticket = 0;  // ... by scrubs up to this number
+    uint64_t tag = 0;     // the driver's alias address of the buffer (0: none)
+    uint16_t n = 1;
+    uint16_t bucket = 0;  // longest free run (0: none free, not in by_run_)
   };
   struct IdleInfo {
     uint64_t seq;
-    uint8_t n;
+    uint16_t n;
     bool used;
-    uint64_t tag, clean_mask, ticket;
+    uint64_t tag;
+    PieceMask clean_mask;
+    uint64_t ticket;
     uint64_t order = 0; // key in idle_n_
   };
   struct Victim {
@@ -420,42 +529,27 @@ private:
   // a single-page pool passes whatever its driver returns through untouched (ROCr's handles use the high bits).
   phys_handle_t key_of(phys_handle_t h) const { return kmax_cfg_ > 1 ? chunk_of(h) : h; }
   unsigned idx_of(phys_handle_t h) const { return kmax_cfg_ > 1 ? piece_of(h) : 0; }
-  static uint64_t full_mask(unsigned n) { return n >= 64 ? ~0ull : ((1ull << n) - 1); }
-  // lowest start of `want` consecutive set bits, or -1
-  static int find_run(uint64_t mask, unsigned want) {
-    uint64_t m = mask;
-    for (unsigned s = 1; s < want && m; ++s) m &= mask >> s;
-    return m ? __builtin_ctzll(m) : -1;
-  }
-  static unsigned longest_run(uint64_t mask) {
-    unsigned n = 0;
-    while (mask) {
-      mask &= mask << 1;
-      ++n;
-    }
-    return n;
-  }
   void unbucket_locked(phys_handle_t h, Extent &e) {
     if (e.bucket) by_run_[e.bucket].erase(h);
     e.bucket = 0;
   }
   void rebucket_locked(phys_handle_t h, Extent &e) {
-    const unsigned b = longest_run(e.free_mask);
+    const unsigned b = e.free_mask.longest_run();
     if (b == e.bucket) return;
     unbucket_locked(h, e);
-    e.bucket = (uint8_t)b;
+    e.bucket = (uint16_t)b;
     if (b) by_run_[b].insert(h);
   }
   // hands out pieces [first, first+n) of a tracked extent
   size_t take_pieces_locked(phys_handle_t h, Extent &e, unsigned first, unsigned n, Phys *out, bool *recycled) {
     unsigned old = 0;
     for (unsigned i = 0; i < n; ++i) {
-      const uint64_t bit = 1ull << (first + i);
-      e.free_mask &= ~bit;
-      old += (e.used_mask & bit) != 0;
-      e.used_mask |= bit;
-      out[i] = Phys{piece_id(h, first + i, e.n), e.seq, (e.clean_mask & bit) ? std::max<uint64_t>(e.ticket, 1) : 0, e.ticket};
-      e.clean_mask &= ~bit; // in somebody's hands now
+      const unsigned p = first + i;
+      e.free_mask.reset(p);
+      old += e.used_mask.test(p);
+      e.used_mask.set(p);
+      out[i] = Phys{piece_id(h, p, e.n), e.seq, e.clean_mask.test(p) ? std::max<uint64_t>(e.ticket, 1) : 0, e.ticket};
+      e.clean_mask.reset(p); // in somebody's hands now
     }
     free_pieces_ -= n;
     out_pieces_ += n;
@@ -468,7 +562,7 @@ private:
   }
   size_t take_free_run_locked(phys_handle_t h, unsigned n, Phys *out, bool *recycled) {
     Extent &e = tracked_[h];
-    const int first = find_run(e.free_mask, n);
+    const int first = e.free_mask.find_run(n);
     return take_pieces_locked(h, e, (unsigned)first, n, out, recycled);
   }
   // an idle extent of exactly `size` pages (the youngest), `take` pieces of it handed out
@@ -482,16 +576,16 @@ private:
     const auto key = *pos;
     s.erase(pos);
     const phys_handle_t h = key.second;
-    const IdleInfo info = idle_info_[h];
+    const IdleInfo info = std::move(idle_info_[h]);
     idle_all_.erase({info.seq, h});
     idle_info_.erase(h);
     idle_pages_ -= size;
     low_water_ = std::min(low_water_, idle_pages_);
     Extent &e = tracked_[h];
     e.seq = info.seq;
-    e.n = (uint8_t)size;
-    e.free_mask = full_mask(size);
-    e.used_mask = info.used ? full_mask(size) : 0;
+    e.n = (uint16_t)size;
+    e.free_mask = PieceMask::full(size);
+    e.used_mask = info.used ? PieceMask::full(size) : PieceMask(size);
     e.bucket = 0;
     e.tag = info.tag;
     e.clean_mask = info.clean_mask;

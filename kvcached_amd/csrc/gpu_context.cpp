@@ -185,7 +185,7 @@ ExtentPool *GpuContext::extents(size_t page_bytes, bool exportable) {
   unsigned k = 1;
   if (!exportable && vmm_backend() == kVmmDrm && DrmVm::instance().kfd_ready() && DrmVm::instance().can_clear())
     k = (unsigned)std::min<int64_t>(kMaxExtentPages, std::max<int64_t>(1, options().phys_chunk_pages.load()));
-  k = (unsigned)std::min<size_t>(k, std::max<size_t>(1, (256u << 20) / page_bytes)); // no buffer above 256 MiB (8 MiB pages, compound pages)
+  k = (unsigned)std::min<size_t>(k, std::max<size_t>(1, (2048ull << 20) / page_bytes)); // no buffer above 2 GiB (8 MiB pages, compound pages)
   std::unique_ptr<ExtentPool> old; // destroyed (drained) after mu_ is released: ~ExtentPool waits for scrubs, whose harvest takes mu_
   ExtentPool *p;
   {
@@ -225,7 +225,7 @@ ExtentPool *GpuContext::lane_extents(size_t rows, size_t page_bytes) {
   // 7 lanes per straggler (64-lane buffers of a small geometry pinned 1 GiB each in tests/test_gpu_colocation.py), and
   // beyond 8 the gain is small (the ioctl count per call is rows x ceil(ids / lanes): 64 for 8 page ids either way).
   const size_t cap_b = (size_t)std::max<int64_t>(1, env_i64("KVCACHED_LANE_EXTENT_MB", 1024)) << 20;
-  const size_t want_k = (size_t)std::min<int64_t>(kMaxExtentPages, std::max<int64_t>(1, env_i64("KVCACHED_LANES_PER_BUFFER", 8)));
+  const size_t want_k = (size_t)std::min<int64_t>(kMaxLanesPerBuffer, std::max<int64_t>(1, env_i64("KVCACHED_LANES_PER_BUFFER", 8)));
   const unsigned k = (unsigned)std::min<size_t>(want_k, std::max<size_t>(1, cap_b / lane_bytes));
   std::unique_ptr<ExtentPool> old;
   ExtentPool *p;
@@ -502,7 +502,7 @@ phys_handle_t GpuContext::zero_extent(size_t page_bytes, size_t *pages) {
   }
   if (vmm_backend() != kVmmDrm || !DrmVm::instance().kfd_ready() || !DrmVm::instance().can_clear()) return 0;
   // 64 pages (128 MiB of zeros for 2 MiB pages: 0.04 % of the HBM), never more than 256 MiB
-  const size_t n = std::max<size_t>(1, std::min<size_t>(kMaxExtentPages, (256u << 20) / page_bytes));
+  const size_t n = std::max<size_t>(1, std::min<size_t>(64, (256u << 20) / page_bytes));
   phys_handle_t h = 0;
   uint64_t alias = 0;
   try {

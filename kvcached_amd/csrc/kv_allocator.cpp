@@ -377,7 +377,7 @@ void KvAllocator::init(const std::string &dev_str, size_t page_size, bool contig
   options().async_shootdown = env_bool("KVCACHED_ASYNC_SHOOTDOWN", true) ? 1 : 0;
   options().hip_reg_group_mb = std::max<int64_t>(0, env_i64("KVCACHED_HIP_REG_GROUP_MB", 64));
   options().clear_run_slots = std::max<int64_t>(0, env_i64("KVCACHED_DRM_CLEAR_RUN", 16));
-  options().phys_chunk_pages = std::min<int64_t>(kMaxExtentPages, std::max<int64_t>(1, env_i64("KVCACHED_PHYS_CHUNK_PAGES", 64)));
+  options().phys_chunk_pages = std::min<int64_t>(kMaxExtentPages, std::max<int64_t>(1, env_i64("KVCACHED_PHYS_CHUNK_PAGES", kMaxExtentPages)));
   options().extent_waste_pct = std::min<int64_t>(100, std::max<int64_t>(0, env_i64("KVCACHED_EXTENT_WASTE_PCT", 5)));
   options().phys_reserve_bytes = std::max<int64_t>(0, env_i64("KVCACHED_PHYS_RESERVE_MB", 2048)) << 20;
   options().scrub_on_release = env_bool("KVCACHED_SCRUB_ON_RELEASE", true) ? 1 : 0;
@@ -703,7 +703,9 @@ bool KvAllocator::prt_all(KvRegion &r, bool by_default) {
     if (vmm_hip_registered()) register_slot(r, i);
   // One mapping per group of 64 slots (2 304 ioctls for the 147 k slots of a 288 GiB reservation), not one for the region:
   // a page-table entry carries a fragment size that may be as large as its MAPPING, and when a mapping is split what is
-  // left of it has to be written again (DrmVm::refresh_prt_remainders) - that stays a matter of <= 64 entries.
+  // left of it has to be written again (DrmVm::refresh_prt_remainders). Runs that go back to PRT later are one mapping of
+  // up to KvRegion::kPrtRunSlots (1024) slots; rewriting what a split leaves of one costs 17 us against 11 us for a
+  // 64-slot group (profiles/r04_prt_run_probe.log): it grows with the length, slowly.
   const size_t group = KvRegion::kPrtGroupSlots * r.page_size;
   for (size_t off = 0; off < r.size; off += group) {
     const int rc = DrmVm::instance().map_prt(r.base + off, std::min(group, r.size - off));
@@ -1450,21 +1452,29 @@ void KvAllocator::map_slots(const std::vector<Slot> &slots, const std::vector<ph
       sg.mark(2);
       for (const SlotRun &run : runs) {
         KvRegion &r = *run.r;
+        // A region whose map path owes no invalidation (lazy mode: plain unmapped VA behind unbacked slots) keeps its mappings
+        // at 512 MiB at most. Observed: a 2 GiB lazy map of recycled extent pages, with no invalidation on the map path, faulted
+        // on its first read (tests/test_gpu_vmm.py::test_async_unmap_queue_reclaimer_and_rebacking); at <= 512 MiB it does
+        // not. Not established why. One candidate: a run of 1 GiB or more may be written as a 1 GiB page-directory entry
+        // where the TLBs still hold a pointer to a table. Regions with a rest mapping invalidate after their REPLACE anyway
+        // and take whole batches.
+        const size_t max_run = r.rest_direct() ? (size_t)-1 : std::max<size_t>(1, (512u << 20) / ps);
         for (size_t at = run.first, end = run.first + run.count; at < end;) { // as many neighbours as one extent can serve at a time
           const int64_t t1 = now_ns();
           bool recycled = false;
           size_t prescrubbed = 0;
           sg.mark(5);
-          size_t n = pool->acquire_run(end - at, got.data(), &recycled, false);
+          const size_t want = std::min(end - at, max_run);
+          size_t n = pool->acquire_run(want, got.data(), &recycled, false);
           if (n == 0 && steal_pending(ps, &got[0])) {
             n = 1; // (its unmap has set tlb_stale: flushed before the fill)
             need_epoch = ctx->next_flush_epoch();
           }
           if (n == 0 && ctx->limbo_bytes()) { // pages of an earlier unmap wait for their invalidation: have it now rather than create
             ctx->flush_limbo();
-            n = pool->acquire_run(end - at, got.data(), &recycled, false);
+            n = pool->acquire_run(want, got.data(), &recycled, false);
           }
-          if (n == 0) n = pool->acquire_run(end - at, got.data(), &recycled, true);
+          if (n == 0) n = pool->acquire_run(want, got.data(), &recycled, true);
           const int64_t t2 = now_ns();
           sg.mark(3);
           char *va = r.base + at * ps;
@@ -1886,7 +1896,7 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
   struct Chunk {
     size_t p, k, rows_done;
     bool settled; // the slots name the lanes
-    Phys lane[kMaxExtentPages];
+    Phys lane[kMaxLanesPerBuffer];
   };
   std::vector<Chunk> done;
   std::vector<void *> pending;
@@ -2300,7 +2310,7 @@ bool KvAllocator::map_imported_page_ids(const offset_t *offsets, size_t n, const
     const offset_t off = offsets[i];
     if (off < 0 || (size_t)off % ps != 0 || (size_t)off / ps >= ids_per_row_) throw InvalidError("offset " + std::to_string(off) + " is not a page id of this geometry");
     const int64_t b = meta[3 * i], k = meta[3 * i + 1], j = meta[3 * i + 2];
-    if (b < 0 || (size_t)b >= n_fds || k < 1 || k > (int64_t)kMaxExtentPages || j < 0 || j >= k)
+    if (b < 0 || (size_t)b >= n_fds || k < 1 || k > (int64_t)kMaxLanesPerBuffer || j < 0 || j >= k)
       throw InvalidError("import of a page id: (fd " + std::to_string(b) + ", lane " + std::to_string(j) + " of " + std::to_string(k) + ") names no lane of the buffers that came along");
     ids[i] = Id{(size_t)off / ps, (uint64_t)b, (uint64_t)k, (uint64_t)j};
     for (const Row &row : rows_)

@@ -25,6 +25,8 @@
 
 namespace kvc {
 
+constexpr unsigned kMaxLanesPerBuffer = 64; // KVCACHED_LANES_PER_BUFFER at most (a lane buffer is rows x lanes pages)
+
 struct Options {
   std::atomic<int64_t> zero_backfill{0};
   std::atomic<int64_t> zero_fill{1};
@@ -36,7 +38,7 @@ struct Options {
   std::atomic<int64_t> async_shootdown{1};       // with a housekeeping thread around, unmap leaves its TLB invalidation to it
   std::atomic<int64_t> hip_reg_group_mb{64};     // hybrid/drm: VA introduced to HIP per hipMemMap (0 = slot by slot)
   std::atomic<int64_t> clear_run_slots{16};      // drm backend: unmap runs of adjacent slots with one CLEAR ioctl (0 = off)
-  std::atomic<int64_t> phys_chunk_pages{64};     // drm backend: a run of adjacent slots is backed by ONE buffer of up to this many pages (1 = off)
+  std::atomic<int64_t> phys_chunk_pages{kMaxExtentPages}; // drm backend: a run of adjacent slots is backed by ONE buffer of up to this many pages (1 = off)
   std::atomic<int64_t> extent_waste_pct{5};      // ... and new extents shrink while free pieces of partly used ones exceed this share of the pages in use
   std::atomic<int64_t> phys_reserve_bytes{0};    // idle physical memory the housekeeping thread keeps ready (pre-created, never below it)
   std::atomic<int64_t> map_waits_for_all_flushes{0}; // 1 = a map batch waits for every invalidation owed, not only those of its own slots
@@ -302,10 +304,13 @@ struct KvRegion {
   // `backfilled` says whether an unmap invalidates inside the call (compat) or behind it (lazy).
   bool prt = false;
   bool rest_direct() const { return zx || prt; }                       // unbacked slots carry a DRM mapping of ours
-  // a REPLACE back to the rest state must not cross a multiple of this: the zero extent's pages repeat with that period,
-  // and PRT mappings are kept to groups so that what a split leaves to be rewritten (DrmVm::refresh_prt_remainders) is small
-  static constexpr size_t kPrtGroupSlots = 64;
-  size_t rest_group() const { return zx ? zx_pages : (prt ? kPrtGroupSlots : (size_t)-1); }
+  // a REPLACE back to the rest state must not cross a multiple of this: the zero extent's pages repeat with that period.
+  // PRT: the reservation lays its mappings out in groups of kPrtGroupSlots (prt_all); a run that goes back to PRT later is
+  // ONE mapping of up to kPrtRunSlots - one batch of run-sized extents (§4.8) - so that an unmap costs one REPLACE per run
+  // and not one per group. What a later split leaves of such a mapping is rewritten by one PRT operation: 17 us after a
+  // split of 1024 slots against 11 us after one of 64 (DrmVm::refresh_prt_remainders, profiles/r04_prt_run_probe.log).
+  static constexpr size_t kPrtGroupSlots = 64, kPrtRunSlots = 1024;
+  size_t rest_group() const { return zx ? zx_pages : (prt ? kPrtRunSlots : (size_t)-1); }
   std::vector<phys_handle_t> handle;   // per slot, valid when mapped[slot]
   std::vector<uint64_t> seq;           // per slot: creation order of that handle (release oldest first)
   std::vector<uint64_t> stale_epoch;   // per slot: the TLB invalidation (GpuContext::next_flush_epoch) that covers its last unmap
