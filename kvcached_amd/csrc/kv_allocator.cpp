@@ -516,12 +516,12 @@ KvAllocator::~KvAllocator() {
   if (!rows_.empty())
     for (size_t p = 0; p < ids_per_row_; ++p) {
       const size_t idx = rows_[0].first + p;
-      if (rows_[0].r->mapped[idx] == 4) lanes.push_back(Phys{rows_[0].r->handle[idx], rows_[0].r->seq[idx]});
-      if (rows_[0].r->mapped[idx] == 5) peers_buffers.push_back(rows_[0].r->handle[idx]);
+      if (rows_[0].r->mapped[idx] == Lane) lanes.push_back(Phys{rows_[0].r->handle[idx], rows_[0].r->seq[idx]});
+      if (rows_[0].r->mapped[idx] == PeerLane) peers_buffers.push_back(rows_[0].r->handle[idx]);
     }
   for (auto &r : layers_) {
-    for (auto m : r->mapped) still_queued += (m == 3) ? r->page_size : 0;
-    destroy_region(*r); // also unmaps what was still queued (state 3 counts as mapped there)
+    for (auto m : r->mapped) still_queued += (m == UnmapQueued) ? r->page_size : 0;
+    destroy_region(*r); // also unmaps what was still queued (UnmapQueued counts as mapped there)
   }
   g_pending_unmap_bytes -= std::min(still_queued, g_pending_unmap_bytes.load());
   layers_.clear();
@@ -569,8 +569,8 @@ void KvAllocator::reclaimer_loop() {
     while (!pending_.empty() && chunk.size() < kChunk) {
       Slot s = pending_.front();
       pending_.pop_front();
-      if (s.region->mapped[s.index] == 3) { // still released (not re-backed, not already handled via a duplicate entry)
-        s.region->mapped[s.index] = 1;
+      if (s.region->mapped[s.index] == UnmapQueued) { // still released (not re-backed, not already handled via a duplicate entry)
+        s.region->mapped[s.index] = Own;
         chunk.push_back(s);
       }
     }
@@ -584,7 +584,7 @@ void KvAllocator::reclaimer_loop() {
       if (dev_.is_gpu) {
         unmap_collect(chunk, u);
       } else {
-        for (auto &c : chunk) c.region->mapped[c.index] = 0;
+        for (auto &c : chunk) c.region->mapped[c.index] = Unbacked;
         stats().pages_unmapped += (int64_t)chunk.size();
       }
     } catch (const std::exception &e) {
@@ -673,7 +673,7 @@ std::unique_ptr<KvRegion> KvAllocator::make_region(const std::string &name, size
   r->handle.assign(r->num_slots(), phys_handle_t{});
   r->seq.assign(r->num_slots(), 0);
   r->stale_epoch.assign(r->num_slots(), 0);
-  r->mapped.assign(r->num_slots(), 0);
+  r->mapped.assign(r->num_slots(), Unbacked);
   r->mark.assign((r->num_slots() + 63) / 64, 0);
   r->registered.assign(r->num_slots(), 0);
   r->reg_group = std::max<size_t>(1, (size_t)std::max<int64_t>(0, options().hip_reg_group_mb.load()) * (1u << 20) / r->page_size);
@@ -913,9 +913,9 @@ void KvAllocator::destroy_region(KvRegion &r) {
     if (!whole) {
       if (!vmm_try_unmap(r.base + i * r.page_size, r.page_size, r.handle[i])) KVC_LOG(LOG_ERROR, "unmap during cleanup failed (slot %zu)", i);
     }
-    if (r.mapped[i] != 4 && r.mapped[i] != 5) // (4 / 5: a page of a lane / of a peer's lane - released once, from ~KvAllocator, not once per row)
-      (r.mapped[i] != 2 ? pieces : dead).push_back(Phys{r.handle[i], r.seq[i]});
-    r.mapped[i] = 0;
+    if (r.mapped[i] != Lane && r.mapped[i] != PeerLane) // (a page of a lane / of a peer's lane is released once, from ~KvAllocator, not once per row)
+      (r.mapped[i] != Imported ? pieces : dead).push_back(Phys{r.handle[i], r.seq[i]});
+    r.mapped[i] = Unbacked;
   }
   std::sort(dead.begin(), dead.end(), [](const Phys &a, const Phys &b) { return a.seq < b.seq; }); // oldest first
   if (r.backfilled && !whole) // aliases that could not be dropped in one call
@@ -1059,7 +1059,7 @@ void KvAllocator::copy_blocks_host(bool to_host, const int64_t *ids, size_t n, s
       const size_t first = sp.off + (size_t)ids[i] * block_bytes, last = first + block_bytes - 1;
       for (size_t slot = first / ps; slot <= last / ps; ++slot) {
         const uint8_t st = sp.r->mapped[slot];
-        if (st != 1 && st != 2 && st != 4 && st != 5)
+        if (st != Own && st != Imported && st != Lane && st != PeerLane)
           throw InvalidError("block id " + std::to_string(ids[i]) + " lies on a slot of " + sp.r->name + " that is not backed");
       }
     }
@@ -1154,11 +1154,11 @@ bool KvAllocator::unmap_from_kv_tensors(const offset_t *offsets, size_t n) {
     size_t queued = 0;
     for (auto &s : slots) {
       uint8_t &m = s.region->mapped[s.index];
-      if (m == 1) {
-        m = 3;
+      if (m == Own) {
+        m = UnmapQueued;
         pending_.push_back(s);
         ++queued;
-      } else if (m == 2) {
+      } else if (m == Imported) {
         now.push_back(s);
       } else { // reference: log + skip (ftensor.cpp:124-127)
         KVC_LOG(LOG_ERROR, "Page %zu is not mapped.", s.index);
@@ -1188,7 +1188,7 @@ bool KvAllocator::steal_pending(size_t ps, Phys *out) {
     Slot s = pending_.front();
     pending_.pop_front();
     KvRegion &r = *s.region;
-    if (r.mapped[s.index] != 3 || r.page_size != ps) continue;
+    if (r.mapped[s.index] != UnmapQueued || r.page_size != ps) continue;
     const int64_t t0 = now_ns();
     if (r.rest_direct() && vmm_direct_bo(r.handle[s.index])) {
       if (rest_replace(r, s.index, 1) != 0) throw GpuError("putting a released slot back into its rest state failed");
@@ -1199,7 +1199,7 @@ bool KvAllocator::steal_pending(size_t ps, Phys *out) {
     if (vmm_extent_pages(r.handle[s.index]) > 1) // one page out of a larger mapping: see unmap_collect
       if (void *bo = vmm_direct_bo(r.handle[s.index])) (void)DrmVm::instance().refresh_mappings_of(bo, ps);
     stats().t_unmap += now_ns() - t0;
-    r.mapped[s.index] = 0;
+    r.mapped[s.index] = Unbacked;
     r.stale_epoch[s.index] = ctx_->next_flush_epoch();
     *out = Phys{r.handle[s.index], r.seq[s.index]};
     g_pending_unmap_bytes -= std::min(ps, g_pending_unmap_bytes.load());
@@ -1212,51 +1212,88 @@ bool KvAllocator::steal_pending(size_t ps, Phys *out) {
 using SlotRun = SlotRunOf<KvRegion>;
 using RunScan = RunScanOf<KvRegion>;
 
-// The hot loop. Per slot: [register with HIP, once per 64 MiB group] -> [unmap the zero alias] -> pooled handle -> map
-// (drm backend: one GEM_VA ioctl; else map + one set_access per contiguous run); zero_fill_pages launches that run on
-// the GPU while the host keeps issuing driver calls for the next slots (3/4 of the batch, then the rest); a TLB
-// invalidation before the first fill only if one is owed; one stream sync at the end.
-void KvAllocator::map_slots(const std::vector<Slot> &slots, const std::vector<phys_handle_t> *imported,
-                            std::vector<uint8_t> *imported_consumed) {
-  if (slots.empty()) return;
-  if (!dev_.is_gpu) { // reference CPUPage::map is a no-op (page.cpp:34-37); keep the double-map diagnostics
-    for (auto &s : slots) {
-      if (s.region->mapped[s.index] == 3) { // async unmap: released, not yet reclaimed -> kept
-        s.region->mapped[s.index] = 1;
-        g_pending_unmap_bytes -= std::min(s.region->page_size, g_pending_unmap_bytes.load());
-        stats().unmaps_cancelled++;
-        stats().pages_mapped++;
-        continue;
-      }
-      if (s.region->mapped[s.index]) {
-        KVC_LOG(LOG_ERROR, "Page %zu is already mapped.", s.index);
-        continue;
-      }
-      s.region->mapped[s.index] = 1;
-      stats().pages_mapped++;
-    }
-    return;
+// Pages for `want` adjacent slots - at least one, at most `want`: the caller comes back for the rest - from the cheapest
+// source that has any: what the pool holds idle; where the caller allows it (`stolen` != nullptr; async unmap) the page of
+// a slot that is released but not yet unmapped, instead of creating one - a single page, so never where the unit is a
+// lane; pages of an earlier unmap that wait for their invalidation - have it now rather than create; new memory.
+// *stolen: the page's old address was live a moment ago (steal_pending has set tlb_stale): the caller waits for the
+// invalidation that starts from now before the page is used.
+size_t KvAllocator::acquire_pages(ExtentPool *pool, size_t want, Phys *out, bool *stolen) {
+  bool recycled = false;
+  size_t n = pool->acquire_run(want, out, &recycled, false);
+  if (n) return n;
+  if (stolen && (*stolen = steal_pending(pool->page_bytes(), out))) return 1;
+  if (ctx_->limbo_bytes()) {
+    ctx_->flush_limbo();
+    n = pool->acquire_run(want, out, &recycled, false);
+    if (n) return n;
   }
-  GpuContext *ctx = ctx_;
-  ctx->bind();
-  const size_t ps = slots[0].region->page_size;
-  ExtentPool *pool = ctx->extents(ps, exportable_);
-  if (!exportable_ && !imported && !ctx->primary_pool()) ctx->set_primary_pool(pool); // the engine's own pool: the reserve is its
-  const bool cold = pool->creations() == 0;
-  const bool fill = options().zero_fill.load() && !imported;
-  const size_t kMaxRunBytes = ps * (size_t)std::max<int64_t>(1, options().access_run_slots.load());
+  return pool->acquire_run(want, out, &recycled, true);
+}
 
-  std::vector<Slot> done;
-  done.reserve(slots.size());
-  std::vector<void *> pending, run_pages;
-  char *run_start = nullptr;
-  size_t run_len = 0;
-  bool launched = false;
-  size_t next_import = 0;
+namespace {
+// Settles a map batch: nothing may reach its new pages through a stale translation of their own addresses. What the
+// batch's REPLACEs split - PRT mappings, the zero extent's group mappings (§4.8's hazard) - still carries fragments that
+// span the new pages and is rewritten before the invalidation that covers it (DrmVm::refresh_prt_remainders,
+// refresh_mappings_of). `replaced`: a translation this batch replaced (or, KVCACHED_MAP_SHOOTDOWN=always, made) is owed an
+// invalidation that the caller has not noted in tlb_stale / need_epoch yet. Then only the invalidations that cover THESE
+// slots' last unmaps have to be waited for (`need_epoch`): a stale translation of some other address cannot shadow a mapping
+// made here, and it is gone a moment later anyway (every unmap batch has its invalidation under way on the context's
+// thread). KVCACHED_MAP_WAITS_FOR_ALL_FLUSHES=true restores the blanket wait.
+void settle_batch(GpuContext *ctx, size_t ps, bool &prt_dirty, void *&zx_dirty, uint64_t &need_epoch, bool replaced) {
+  const int64_t t_rw = now_ns();
+  if (prt_dirty) {
+    if (!KVC_TEST_HOOK("SKIP_PRT_REMAINDER_REFRESH") && !DrmVm::instance().refresh_prt_remainders()) // (hook: prove the test has teeth)
+      throw GpuError("rewriting the remainders of split PRT mappings failed");
+    prt_dirty = false;
+    replaced = true;
+  }
+  if (zx_dirty) {
+    if (!DrmVm::instance().refresh_mappings_of(zx_dirty, ps)) KVC_LOG(LOG_ERROR, "rewriting the remaining mappings of the zero extent failed");
+    zx_dirty = nullptr;
+    replaced = true;
+  }
+  stats().seg[20] += now_ns() - t_rw;
+  if (replaced) {
+    tlb_stale().store(true);
+    need_epoch = ctx->next_flush_epoch();
+  }
+  if (options().map_waits_for_all_flushes.load() || options().map_shootdown_always.load())
+    ctx->ensure_flushed();
+  else
+    ctx->ensure_flushed_through(need_epoch);
+}
 
-  // Pages become usable in chunks: driver calls for <=`chunk` slots, ONE TLB shootdown (its cost grows only
-  // mildly with the number of new mappings: 0.31 ms @256, 0.40 ms @1024), then the fill kernel
-  // for exactly those slots runs on the GPU while the host issues the driver calls of the next chunk.
+// A map batch failed: `undo` takes its mappings back - once no fill can still be running on the pages that go - and no
+// translation of them is left behind, nor the error HIP remembers.
+template <class Undo> void roll_back(GpuContext *ctx, bool launched, Undo &&undo) {
+  if (launched) (void)hipStreamSynchronize(ctx->stream());
+  undo();
+  (void)hipGetLastError();
+  try {
+    ctx->tlb_shootdown();
+  } catch (...) {
+  }
+}
+} // namespace
+
+// The state of one map_slots() batch on the GPU. Per slot: [register with HIP, once per 64 MiB group] -> [unmap the zero
+// alias] -> pooled handle -> map (drm backend: one GEM_VA ioctl; else map + one set_access per contiguous run);
+// zero_fill_pages launches that run on the GPU while the host keeps issuing driver calls for the next slots (3/4 of the
+// batch, then the rest); a TLB invalidation before the first fill only if one is owed; one stream sync at the end.
+struct KvAllocator::MapBatch {
+  KvAllocator &a;
+  GpuContext *const ctx;
+  const size_t ps;
+  ExtentPool *const pool;
+  const std::vector<phys_handle_t> *const imported; // a peer's pages, one per slot, instead of pages from the pool
+  std::vector<uint8_t> *const imported_consumed;
+  const bool fill;
+  const size_t max_run_bytes;
+  // Run-sized extents (KVCACHED_PHYS_CHUNK_PAGES > 1, drm backend): the unbacked slots of the batch are collected
+  // first and then backed run by run - adjacent slots get adjacent pages of one buffer and ONE map ioctl.
+  const bool chunked;
+  const bool hip_reg = vmm_hip_registered();
   // A TLB invalidation is owed before the new pages are touched only where a translation of these VAs (or of these
   // pages) may still sit in a TLB: an unmap whose invalidation was deferred, a slot whose zero alias or PRT entry is
   // being replaced, a page taken from a slot that was released but not yet unmapped. The translation of an UNMAPPED
@@ -1265,36 +1302,13 @@ void KvAllocator::map_slots(const std::vector<Slot> &slots, const std::vector<ph
   // a plain map of an unmapped slot whose last unmap was invalidated needs nothing (KVCACHED_MAP_SHOOTDOWN=always
   // restores it). A PRT entry is another matter: cached once looked at (tools/prt_tlb_probe.cpp).
   const bool always_flush = options().map_shootdown_always.load() != 0;
-  bool dirty_tlb = ctx->tlb_owed(); // an invalidation is owed before anything of this batch is touched
-  // ... but only the invalidations that cover THESE slots' last unmaps have to be waited for: a stale translation of some
-  // other address cannot shadow a mapping made here, and it is gone a moment later anyway (every unmap batch has its
-  // invalidation under way on the context's thread). KVCACHED_MAP_WAITS_FOR_ALL_FLUSHES=true restores the blanket wait.
-  uint64_t need_epoch = 0;
-  for (auto &s : slots) need_epoch = std::max(need_epoch, s.region->stale_epoch[s.index]);
-  const bool blanket = options().map_waits_for_all_flushes.load() != 0;
+  bool dirty_tlb;           // an invalidation is owed before anything of this batch is touched
+  uint64_t need_epoch = 0;  // ... and it is this one (settle_batch)
   void *zx_dirty = nullptr; // compat mode, zero extent: its group mappings were split by this batch's REPLACEs (§4.8's hazard)
   bool prt_dirty = false;   // PRT mappings were split by this batch: what is left of them carries fragments that span the new pages
-  auto flush_for_batch = [&]() {
-    const int64_t t_rw = now_ns();
-    if (prt_dirty) { // rewritten before the invalidation that covers them (DrmVm::refresh_prt_remainders)
-      if (!KVC_TEST_HOOK("SKIP_PRT_REMAINDER_REFRESH") && !DrmVm::instance().refresh_prt_remainders()) // (hook: prove the test has teeth)
-        throw GpuError("rewriting the remainders of split PRT mappings failed");
-      tlb_stale().store(true);
-      need_epoch = ctx->next_flush_epoch();
-      prt_dirty = false;
-    }
-    if (zx_dirty) { // the remainders of the zero extent's mappings are rewritten before the invalidation that covers them
-      if (!DrmVm::instance().refresh_mappings_of(zx_dirty, ps)) KVC_LOG(LOG_ERROR, "rewriting the remaining mappings of the zero extent failed");
-      tlb_stale().store(true);
-      need_epoch = ctx->next_flush_epoch();
-      zx_dirty = nullptr;
-    }
-    stats().seg[20] += now_ns() - t_rw;
-    if (blanket || always_flush)
-      ctx->ensure_flushed();
-    else
-      ctx->ensure_flushed_through(need_epoch);
-  };
+  // Pages become usable in chunks: driver calls for <=`chunk` slots, ONE TLB shootdown (its cost grows only
+  // mildly with the number of new mappings: 0.31 ms @256, 0.40 ms @1024), then the fill kernel
+  // for exactly those slots runs on the GPU while the host issues the driver calls of the next chunk.
   // Fill launches: the kernel for the slots mapped so far runs while the host issues the driver calls for the rest, so
   // only the LAST launch is exposed. Large launches are more efficient (ramp and tail are ~10 us whatever the size:
   // 6.8 TB/s at 2 GiB, 6.4 at 512 MiB), the exposed one should be short: a batch of n >= 512 slots is filled as
@@ -1302,26 +1316,53 @@ void KvAllocator::map_slots(const std::vector<Slot> &slots, const std::vector<ph
   // for one launch; p50 map batch 2.85 -> 2.6 ms). KVCACHED_FILL_CHUNK_SLOTS caps a launch (and while a TLB
   // invalidation is owed per chunk - compat mode, deferred unmaps - larger chunks mean fewer of them).
   const size_t chunk = (size_t)std::max<int64_t>(1, options().fill_chunk_slots.load());
-  const size_t n_total = slots.size();
-  // (with run-sized extents the driver calls of a whole batch take less time than a launch: nothing to hide a first
-  // instalment behind, and one large launch is the more efficient one)
-  size_t next_cut = (n_total >= 512 && !pool->multi_page()) ? std::min(chunk, n_total - std::max<size_t>(128, n_total / 4)) : chunk;
+  size_t next_cut;
+  std::vector<void *> pending; // addresses mapped and not yet filled
+  bool launched = false;
   uint64_t max_ticket = 0; // pages that were zeroed on their way back: nothing to launch, only that scrub to wait for
-  auto launch_pending = [&](bool all) {
+  std::vector<void *> run_pages; // mapped, hipMemSetAccess still owed: [run_start, run_start + run_len)
+  char *run_start = nullptr;
+  size_t run_len = 0;
+  size_t next_import = 0;
+  std::vector<Slot> done; // backed by this batch
+  std::vector<Slot> kept; // async unmap: released but not yet unmapped -> simply kept, only zero-filled again
+  SegTimer sg;
+
+  MapBatch(KvAllocator &alloc, const std::vector<Slot> &slots, const std::vector<phys_handle_t> *imp, std::vector<uint8_t> *consumed)
+      : a(alloc), ctx(alloc.ctx_), ps(slots[0].region->page_size), pool(ctx->extents(ps, alloc.exportable_)), imported(imp),
+        imported_consumed(consumed), fill(options().zero_fill.load() && !imp),
+        max_run_bytes(ps * (size_t)std::max<int64_t>(1, options().access_run_slots.load())), chunked(pool->multi_page() && !imp),
+        dirty_tlb(ctx->tlb_owed()) {
+    if (!a.exportable_ && !imported && !ctx->primary_pool()) ctx->set_primary_pool(pool); // the engine's own pool: the reserve is its
+    for (auto &s : slots) need_epoch = std::max(need_epoch, s.region->stale_epoch[s.index]);
+    // (with run-sized extents the driver calls of a whole batch take less time than a launch: nothing to hide a first
+    // instalment behind, and one large launch is the more efficient one)
+    const size_t n_total = slots.size();
+    next_cut = (n_total >= 512 && !pool->multi_page()) ? std::min(chunk, n_total - std::max<size_t>(128, n_total / 4)) : chunk;
+    done.reserve(n_total);
+    sg.t = now_ns();
+  }
+
+  // only if one of these slots (or, compat mode, an alias replaced in this batch) is still owed an invalidation
+  void settle() {
+    settle_batch(ctx, ps, prt_dirty, zx_dirty, need_epoch, always_flush && dirty_tlb);
+    dirty_tlb = false;
+  }
+
+  void launch_pending(bool all) {
     size_t i = 0;
     while (pending.size() - i >= next_cut || (all && i < pending.size())) {
       const size_t end = i + std::min(next_cut, pending.size() - i);
-      if (always_flush && dirty_tlb) tlb_stale().store(true);
-      dirty_tlb = false;
-      flush_for_batch(); // only if one of these slots (or, compat mode, an alias replaced in this batch) is still owed one
+      settle();
       for (; i < end; i += std::min<size_t>(kMaxPtrsPerLaunch, end - i))
         ctx->zero_fill(pending.data() + i, std::min<size_t>(kMaxPtrsPerLaunch, end - i), ps, nullptr);
       launched = true;
       next_cut = chunk; // after the first launch: whatever is left, in launches of at most `chunk`
     }
     pending.erase(pending.begin(), pending.begin() + i);
-  };
-  auto flush_run = [&]() {
+  }
+
+  void flush_run() {
     if (!run_len) return;
     const int64_t ta = now_ns();
     vmm_set_access(run_start, run_len, ctx->dev());
@@ -1333,198 +1374,186 @@ void KvAllocator::map_slots(const std::vector<Slot> &slots, const std::vector<ph
     }
     run_pages.clear();
     run_len = 0;
-  };
+  }
 
-  std::vector<Slot> kept; // async unmap: released but not yet unmapped -> simply kept, only zero-filled again
-  // Run-sized extents (KVCACHED_PHYS_CHUNK_PAGES > 1, drm backend): the unbacked slots of the batch are collected
-  // first and then backed run by run - adjacent slots get adjacent pages of one buffer and ONE map ioctl.
-  const bool chunked = pool->multi_page() && !imported;
-  RunScan fresh;
-  const bool hip_reg = vmm_hip_registered();
-  SegTimer sg;
-  try {
-    for (auto &s : slots) {
-      KvRegion &r = *s.region;
-      if (chunked && r.mapped[s.index] == 0 && (!r.backfilled || r.rest_direct())) { // the common case, nothing per slot but a bit
-        if (hip_reg && !r.registered[s.index]) {
-          const int64_t t0 = now_ns();
-          register_slot(r, s.index); // once per slot
-          stats().t_unmap_alias += now_ns() - t0;
-        }
-        // the same slot listed twice in one call: the reference logs "already mapped" for the second and goes on (ftensor.cpp:104-107)
-        if (!fresh.add(&r, s.index)) KVC_LOG(LOG_ERROR, "Page %zu is already mapped.", s.index);
-        continue; // backed below, run by run: adjacent slots share one ioctl
-      }
-      if (r.mapped[s.index] == 3 && !imported) {
-        r.mapped[s.index] = 1; // its queue entry is dropped by the reclaimer (state no longer 3)
-        kept.push_back(s);
-        g_pending_unmap_bytes -= std::min(ps, g_pending_unmap_bytes.load());
-        stats().unmaps_cancelled++;
-        if (fill) pending.push_back(r.base + s.index * ps);
-        continue;
-      }
-      if (r.mapped[s.index]) { // reference: log + skip, the batch still succeeds (ftensor.cpp:104-107)
-        KVC_LOG(LOG_ERROR, "Page %zu is already mapped.", s.index);
-        if (imported) ++next_import;
-        continue;
-      }
-      char *va = r.base + s.index * ps;
-      int64_t t0 = now_ns();
-      if (hip_reg && !r.registered[s.index]) register_slot(r, s.index); // once per slot
-      if (r.rest_direct() && !chunked) { // (chunked: replaced run by run below)
-        if (DrmVm::instance().clear(va, ps) != 0) throw GpuError("dropping the rest mapping of a slot failed");
-        // a zero alias was a live translation, and so - for the TLBs - is a PRT entry that something has looked at
-        // (tools/prt_tlb_probe.cpp): an invalidation is owed before the page is used
-        tlb_stale().store(true);
-        if (r.zx) zx_dirty = DrmVm::instance().find(r.zx_handle);
-        if (r.prt) prt_dirty = true;
-        dirty_tlb = true;
-        need_epoch = ctx->next_flush_epoch();
-      } else if (r.backfilled && !r.rest_direct()) {
-        vmm_unmap(va, ps);
-        dirty_tlb = true; // the alias's translation is live
-        need_epoch = ctx->next_flush_epoch();
-      }
-      int64_t t1 = now_ns();
-      bool recycled = false;
-      Phys ph;
-      size_t import_index = 0;
-      if (imported) {
-        import_index = next_import;
-        ph = Phys{(*imported)[next_import++], 0};
-      } else if (pool->acquire_run(1, &ph, &recycled, false) == 1) {
-        recycled = true;
-      } else if (steal_pending(ps, &ph)) { // async unmap: take the page of a released slot instead of creating one
-        recycled = true;
+  // A rest mapping of `r` has just been taken away (CLEAR) or replaced. What was there may sit in a TLB: a zero alias is a
+  // live translation (and the split remainders of its mapping are rewritten first), and a PRT entry is cached like one as
+  // soon as anything has read or written the address (tools/prt_tlb_probe.cpp: after a chip-wide read of PRT slots,
+  // backing them without an invalidation left every read stale and lost 0.8 % of the writes). Invalidate before use.
+  void rest_mapping_gone(const KvRegion &r) {
+    if (r.zx) zx_dirty = DrmVm::instance().find(r.zx_handle);
+    if (r.prt) prt_dirty = true;
+    tlb_stale().store(true);
+    dirty_tlb = true;
+    need_epoch = ctx->next_flush_epoch();
+  }
+
+  // A page that was just mapped: what still stands between the caller and zeros in it. True: nothing but a scrub that is
+  // under way (the page was zeroed on its way back) - nothing to launch, only that ticket to wait for; false: it needs a
+  // fill of its own (where one is wanted). (`ticket` by reference: the run loop keeps it in a register.)
+  static bool prescrubbed(bool fill, const Phys &ph, uint64_t &ticket) {
+    ticket = std::max(ticket, ph.wait_ticket); // (any older fill through the alias must be over before the caller writes)
+    if (!fill || !ph.scrub_ticket) return false;
+    ticket = std::max(ticket, ph.scrub_ticket);
+    return true;
+  }
+
+  // Slots that are backed already: true if `s` was one (released but not yet unmapped: kept; anything else: logged, skipped)
+  bool keep_or_skip(const Slot &s) {
+    KvRegion &r = *s.region;
+    if (r.mapped[s.index] == UnmapQueued && !imported) {
+      r.mapped[s.index] = Own; // its queue entry is dropped by the reclaimer (no longer UnmapQueued)
+      kept.push_back(s);
+      g_pending_unmap_bytes -= std::min(ps, g_pending_unmap_bytes.load());
+      stats().unmaps_cancelled++;
+      if (fill) pending.push_back(r.base + s.index * ps);
+      return true;
+    }
+    if (r.mapped[s.index]) { // reference: log + skip, the batch still succeeds (ftensor.cpp:104-107)
+      KVC_LOG(LOG_ERROR, "Page %zu is already mapped.", s.index);
+      if (imported) ++next_import;
+      return true;
+    }
+    return false;
+  }
+
+  // One unbacked slot with driver calls of its own: single-page pools, zero aliases through ROCr, imports
+  void back_slot(const Slot &s) {
+    KvRegion &r = *s.region;
+    char *va = r.base + s.index * ps;
+    int64_t t0 = now_ns();
+    if (hip_reg && !r.registered[s.index]) a.register_slot(r, s.index); // once per slot
+    if (r.rest_direct() && !chunked) { // (chunked: replaced run by run in back_runs())
+      if (DrmVm::instance().clear(va, ps) != 0) throw GpuError("dropping the rest mapping of a slot failed");
+      rest_mapping_gone(r);
+    } else if (r.backfilled && !r.rest_direct()) {
+      vmm_unmap(va, ps);
+      dirty_tlb = true; // the alias's translation is live
+      need_epoch = ctx->next_flush_epoch();
+    }
+    int64_t t1 = now_ns();
+    Phys ph;
+    size_t import_index = 0;
+    if (imported) {
+      import_index = next_import;
+      ph = Phys{(*imported)[next_import++], 0};
+    } else {
+      bool stolen = false;
+      (void)a.acquire_pages(pool, 1, &ph, &stolen);
+      if (stolen) {
         dirty_tlb = true;
         need_epoch = ctx->next_flush_epoch(); // (the page's old address was live a moment ago: conservative)
-      } else {
-        if (ctx->limbo_bytes()) ctx->flush_limbo(); // pages of an earlier unmap wait for their invalidation: have it now rather than create
-        (void)pool->acquire_run(1, &ph, &recycled, true);
       }
-      phys_handle_t h = ph.h;
-      int64_t t2 = now_ns();
-      bool needs_access = true;
-      try {
-        needs_access = vmm_map(va, ps, h);
-      } catch (...) {
-        if (!imported) pool->release(ph);
-        if (r.rest_direct())
-          (void)rest_map(r, s.index, 1); // (its rest mapping was cleared above)
-        else if (r.backfilled && vmm_try_map(va, ps, r.zero_of(s.index)))
-          (void)vmm_try_set_access(va, ps, ctx->dev());
-        throw;
-      }
-      int64_t t3 = now_ns();
-      stats().t_unmap_alias += t1 - t0;
-      stats().t_acquire += t2 - t1;
-      stats().t_map += t3 - t2;
-      r.handle[s.index] = h;
-      r.seq[s.index] = ph.seq;
-      r.mapped[s.index] = imported ? 2 : 1;
-      if (imported && imported_consumed) (*imported_consumed)[import_index] = 1; // the slot owns it now (rollback releases it)
+    }
+    int64_t t2 = now_ns();
+    bool needs_access = true;
+    try {
+      needs_access = vmm_map(va, ps, ph.h);
+    } catch (...) {
+      if (!imported) pool->release(ph);
+      if (r.rest_direct())
+        (void)a.rest_map(r, s.index, 1); // (its rest mapping was cleared above)
+      else if (r.backfilled && vmm_try_map(va, ps, r.zero_of(s.index)))
+        (void)vmm_try_set_access(va, ps, ctx->dev());
+      throw;
+    }
+    int64_t t3 = now_ns();
+    stats().t_unmap_alias += t1 - t0;
+    stats().t_acquire += t2 - t1;
+    stats().t_map += t3 - t2;
+    r.handle[s.index] = ph.h;
+    r.seq[s.index] = ph.seq;
+    r.mapped[s.index] = imported ? Imported : Own;
+    if (imported && imported_consumed) (*imported_consumed)[import_index] = 1; // the slot owns it now (rollback releases it)
+    if (!needs_access) { // mapped readable+writable in one ioctl (drm backend): straight to the fill queue
+      if (always_flush) dirty_tlb = true;
       done.push_back(s);
-      if (!needs_access) { // mapped readable+writable in one ioctl (drm backend): straight to the fill queue
+      if (prescrubbed(fill, ph, max_ticket)) {
+        stats().pages_prescrubbed++;
+      } else if (fill) {
+        pending.push_back(va);
+        launch_pending(false);
+      }
+      return;
+    }
+    done.push_back(s);
+    if (!(run_len && va == run_start + run_len && run_len < max_run_bytes)) {
+      flush_run();
+      run_start = va;
+    }
+    run_len += ps;
+    run_pages.push_back(va);
+  }
+
+  // The fresh slots, run by run: as many neighbours as one extent can serve at a time, one ioctl each
+  void back_runs(const std::vector<SlotRun> &runs) {
+    std::vector<Phys> got(kMaxExtentPages);
+    stats().seg[23] += (int64_t)runs.size();
+    sg.mark(2);
+    for (const SlotRun &run : runs) {
+      KvRegion &r = *run.r;
+      // A region whose map path owes no invalidation (lazy mode: plain unmapped VA behind unbacked slots) keeps its mappings
+      // at 512 MiB at most. Observed: a 2 GiB lazy map of recycled extent pages, with no invalidation on the map path, faulted
+      // on its first read (tests/test_gpu_vmm.py::test_async_unmap_queue_reclaimer_and_rebacking); at <= 512 MiB it does
+      // not. Not established why. One candidate: a run of 1 GiB or more may be written as a 1 GiB page-directory entry
+      // where the TLBs still hold a pointer to a table. Regions with a rest mapping invalidate after their REPLACE anyway
+      // and take whole batches.
+      const size_t max_run = r.rest_direct() ? (size_t)-1 : std::max<size_t>(1, (512u << 20) / ps);
+      for (size_t at = run.first, end = run.first + run.count; at < end;) {
+        const int64_t t1 = now_ns();
+        sg.mark(5);
+        bool stolen = false;
+        const size_t n = a.acquire_pages(pool, std::min(end - at, max_run), got.data(), &stolen);
+        if (stolen) need_epoch = ctx->next_flush_epoch(); // (its unmap has set tlb_stale: flushed before the fill)
+        const int64_t t2 = now_ns();
+        sg.mark(3);
+        char *va = r.base + at * ps;
+        try {
+          if (r.rest_direct()) { // the slots carry their rest mapping: pages take its place in the same ioctl
+            vmm_replace_pieces(va, ps, n, got[0].h, /*live=*/true);
+            rest_mapping_gone(r);
+          } else {
+            vmm_map_pieces(va, ps, n, got[0].h);
+          }
+        } catch (...) {
+          pool->release_batch(got.data(), n);
+          throw;
+        }
+        stats().t_acquire += t2 - t1;
+        stats().t_map += now_ns() - t2;
+        stats().seg[21]++;
+        sg.mark(4);
+        // (per page of the batch: everything this loop updates is a local or the regions' arrays - nothing is re-read
+        // through `this` - and nothing in it can throw while `done` has entries that are not filled in yet)
+        const bool want_fill = fill;
+        uint64_t ticket = max_ticket;
+        size_t clean = 0;
+        done.resize(done.size() + n);
+        Slot *d = done.data() + done.size() - n;
+        for (size_t k = 0; k < n; ++k) {
+          r.handle[at + k] = got[k].h;
+          r.seq[at + k] = got[k].seq;
+          r.mapped[at + k] = Own;
+          d[k] = Slot{&r, at + k};
+          clean += prescrubbed(want_fill, got[k], ticket);
+        }
+        if (want_fill && clean < n) // fresh memory, or pages that came back unscrubbed
+          for (size_t k = 0; k < n; ++k)
+            if (!got[k].scrub_ticket) pending.push_back(r.base + (at + k) * ps);
+        max_ticket = ticket;
+        if (clean) stats().pages_prescrubbed += (int64_t)clean;
         if (always_flush) dirty_tlb = true;
-        max_ticket = std::max(max_ticket, ph.wait_ticket); // (any older fill through the alias must be over before the caller writes)
-        if (fill && ph.scrub_ticket) {
-          max_ticket = std::max(max_ticket, ph.scrub_ticket);
-          stats().pages_prescrubbed++;
-        } else if (fill) {
-          pending.push_back(va);
-          launch_pending(false);
-        }
-        continue;
-      }
-      if (!(run_len && va == run_start + run_len && run_len < kMaxRunBytes)) {
-        flush_run();
-        run_start = va;
-      }
-      run_len += ps;
-      run_pages.push_back(va);
-    }
-    flush_run();
-    sg.mark(1);
-    if (fresh.size()) {
-      std::vector<Phys> got(kMaxExtentPages);
-      const std::vector<SlotRun> runs = fresh.collect();
-      stats().seg[23] += (int64_t)runs.size();
-      sg.mark(2);
-      for (const SlotRun &run : runs) {
-        KvRegion &r = *run.r;
-        // A region whose map path owes no invalidation (lazy mode: plain unmapped VA behind unbacked slots) keeps its mappings
-        // at 512 MiB at most. Observed: a 2 GiB lazy map of recycled extent pages, with no invalidation on the map path, faulted
-        // on its first read (tests/test_gpu_vmm.py::test_async_unmap_queue_reclaimer_and_rebacking); at <= 512 MiB it does
-        // not. Not established why. One candidate: a run of 1 GiB or more may be written as a 1 GiB page-directory entry
-        // where the TLBs still hold a pointer to a table. Regions with a rest mapping invalidate after their REPLACE anyway
-        // and take whole batches.
-        const size_t max_run = r.rest_direct() ? (size_t)-1 : std::max<size_t>(1, (512u << 20) / ps);
-        for (size_t at = run.first, end = run.first + run.count; at < end;) { // as many neighbours as one extent can serve at a time
-          const int64_t t1 = now_ns();
-          bool recycled = false;
-          size_t prescrubbed = 0;
-          sg.mark(5);
-          const size_t want = std::min(end - at, max_run);
-          size_t n = pool->acquire_run(want, got.data(), &recycled, false);
-          if (n == 0 && steal_pending(ps, &got[0])) {
-            n = 1; // (its unmap has set tlb_stale: flushed before the fill)
-            need_epoch = ctx->next_flush_epoch();
-          }
-          if (n == 0 && ctx->limbo_bytes()) { // pages of an earlier unmap wait for their invalidation: have it now rather than create
-            ctx->flush_limbo();
-            n = pool->acquire_run(want, got.data(), &recycled, false);
-          }
-          if (n == 0) n = pool->acquire_run(want, got.data(), &recycled, true);
-          const int64_t t2 = now_ns();
-          sg.mark(3);
-          char *va = r.base + at * ps;
-          try {
-            if (r.rest_direct()) { // the slots carry their rest mapping: pages take its place in the same ioctl
-              vmm_replace_pieces(va, ps, n, got[0].h, /*live=*/true);
-              // What was there may sit in a TLB: a zero alias is a live translation (and the split remainders of its
-              // mapping are rewritten first), and a PRT entry is cached like one as soon as anything has read or written
-              // the address (tools/prt_tlb_probe.cpp: after a chip-wide read of PRT slots, backing them without an
-              // invalidation left every read stale and lost 0.8 % of the writes). Invalidate before use.
-              if (r.zx) zx_dirty = DrmVm::instance().find(r.zx_handle);
-              if (r.prt) prt_dirty = true;
-              tlb_stale().store(true);
-              dirty_tlb = true;
-              need_epoch = ctx->next_flush_epoch();
-            } else {
-              vmm_map_pieces(va, ps, n, got[0].h);
-            }
-          } catch (...) {
-            pool->release_batch(got.data(), n);
-            throw;
-          }
-          stats().t_acquire += t2 - t1;
-          stats().t_map += now_ns() - t2;
-          stats().seg[21]++;
-          sg.mark(4);
-          for (size_t k = 0; k < n; ++k) {
-            const size_t index = at + k;
-            r.handle[index] = got[k].h;
-            r.seq[index] = got[k].seq;
-            r.mapped[index] = 1;
-            done.push_back(Slot{&r, index});
-            max_ticket = std::max(max_ticket, got[k].wait_ticket);
-            if (fill && got[k].scrub_ticket) {
-              max_ticket = std::max(max_ticket, got[k].scrub_ticket);
-              ++prescrubbed;
-            } else if (fill)
-              pending.push_back(r.base + index * ps);
-          }
-          if (prescrubbed) stats().pages_prescrubbed += (int64_t)prescrubbed;
-          if (always_flush) dirty_tlb = true;
-          if (fill) launch_pending(false);
-          at += n;
-        }
+        if (fill) launch_pending(false);
+        at += n;
       }
     }
+  }
+
+  // the last fills, the invalidation if one is still owed, and the wait for everything that was launched or was in flight
+  void finish() {
     sg.mark(5);
     if (fill) launch_pending(true);
-    if (always_flush && dirty_tlb) tlb_stale().store(true);
-    flush_for_batch(); // nothing may reach the new mappings through a stale translation of their own addresses
+    settle(); // nothing may reach the new mappings through a stale translation of their own addresses
     sg.mark(6);
     const int64_t ts = now_ns();
     if (launched) ctx->sync(nullptr);
@@ -1533,40 +1562,86 @@ void KvAllocator::map_slots(const std::vector<Slot> &slots, const std::vector<ph
     stats().t_sync += now_ns() - ts;
     sg.mark(8);
     if (max_ticket) stats().seg[9] += (int64_t)(ctx->scrubs_issued() - max_ticket); // (diagnostics: how many scrubs behind the newest the one waited for was)
-  } catch (...) {
-    // leave the regions as they were before this call; PageAllocator rolls the page ids back
-    if (launched) (void)hipStreamSynchronize(ctx->stream());
-    for (auto &k : kept) { // still in the reclaimer's queue: just hand them back to it
-      k.region->mapped[k.index] = 3;
-      g_pending_unmap_bytes += ps;
-    }
-    for (auto it = done.rbegin(); it != done.rend(); ++it) {
-      KvRegion &r = *it->region;
-      char *va = r.base + it->index * ps;
-      if (r.rest_direct()) { // back to its rest state, the page dropped in the same ioctl
-        (void)rest_replace(r, it->index, 1);
-      } else {
-        (void)vmm_try_unmap(va, ps, r.handle[it->index]);
+  }
+
+  // leave the regions as they were before this call; PageAllocator rolls the page ids back
+  void rollback() {
+    roll_back(ctx, launched, [&]() {
+      for (auto &k : kept) { // still in the reclaimer's queue: just hand them back to it
+        k.region->mapped[k.index] = UnmapQueued;
+        g_pending_unmap_bytes += ps;
       }
-      if (vmm_extent_pages(r.handle[it->index]) > 1)
-        if (void *bo = vmm_direct_bo(r.handle[it->index])) (void)DrmVm::instance().refresh_mappings_of(bo, ps);
-      if (r.mapped[it->index] == 1)
-        pool->release(Phys{r.handle[it->index], r.seq[it->index]});
-      else
-        (void)vmm_try_release(r.handle[it->index]);
-      r.mapped[it->index] = 0;
-      if (r.backfilled && !r.rest_direct() && vmm_try_map(va, ps, r.zero_of(it->index))) (void)vmm_try_set_access(va, ps, ctx->dev());
+      for (auto it = done.rbegin(); it != done.rend(); ++it) {
+        KvRegion &r = *it->region;
+        char *va = r.base + it->index * ps;
+        if (r.rest_direct()) { // back to its rest state, the page dropped in the same ioctl
+          (void)a.rest_replace(r, it->index, 1);
+        } else {
+          (void)vmm_try_unmap(va, ps, r.handle[it->index]);
+        }
+        if (vmm_extent_pages(r.handle[it->index]) > 1)
+          if (void *bo = vmm_direct_bo(r.handle[it->index])) (void)DrmVm::instance().refresh_mappings_of(bo, ps);
+        if (r.mapped[it->index] == Own)
+          pool->release(Phys{r.handle[it->index], r.seq[it->index]});
+        else
+          (void)vmm_try_release(r.handle[it->index]);
+        r.mapped[it->index] = Unbacked;
+        if (r.backfilled && !r.rest_direct() && vmm_try_map(va, ps, r.zero_of(it->index))) (void)vmm_try_set_access(va, ps, ctx->dev());
+      }
+    });
+  }
+};
+
+void KvAllocator::map_slots(const std::vector<Slot> &slots, const std::vector<phys_handle_t> *imported,
+                            std::vector<uint8_t> *imported_consumed) {
+  if (slots.empty()) return;
+  if (!dev_.is_gpu) { // reference CPUPage::map is a no-op (page.cpp:34-37); keep the double-map diagnostics
+    for (auto &s : slots) {
+      if (s.region->mapped[s.index] == UnmapQueued) { // async unmap: released, not yet reclaimed -> kept
+        s.region->mapped[s.index] = Own;
+        g_pending_unmap_bytes -= std::min(s.region->page_size, g_pending_unmap_bytes.load());
+        stats().unmaps_cancelled++;
+        stats().pages_mapped++;
+        continue;
+      }
+      if (s.region->mapped[s.index]) {
+        KVC_LOG(LOG_ERROR, "Page %zu is already mapped.", s.index);
+        continue;
+      }
+      s.region->mapped[s.index] = Own;
+      stats().pages_mapped++;
     }
-    (void)hipGetLastError();
-    try {
-      ctx->tlb_shootdown();
-    } catch (...) {
+    return;
+  }
+  ctx_->bind();
+  MapBatch b(*this, slots, imported, imported_consumed);
+  RunScan fresh; // chunked: the unbacked slots, backed run by run once every slot has been looked at
+  const bool chunked = b.chunked, hip_reg = b.hip_reg;
+  try {
+    for (auto &s : slots) {
+      KvRegion &r = *s.region;
+      if (chunked && r.mapped[s.index] == Unbacked && (!r.backfilled || r.rest_direct())) { // the common case, nothing per slot but a bit
+        if (hip_reg && !r.registered[s.index]) {
+          const int64_t t0 = now_ns();
+          register_slot(r, s.index); // once per slot
+          stats().t_unmap_alias += now_ns() - t0;
+        }
+        // the same slot listed twice in one call: the reference logs "already mapped" for the second and goes on (ftensor.cpp:104-107)
+        if (!fresh.add(&r, s.index)) KVC_LOG(LOG_ERROR, "Page %zu is already mapped.", s.index);
+      } else if (!b.keep_or_skip(s)) {
+        b.back_slot(s);
+      }
     }
+    b.flush_run();
+    b.sg.mark(1);
+    if (fresh.size()) b.back_runs(fresh.collect());
+    b.finish();
+  } catch (...) {
+    b.rollback();
     throw;
   }
-  stats().pages_mapped += (int64_t)(done.size() + kept.size());
-  (void)cold;
-  if (pool->creations() > 0 && !imported && !exportable_) cold_start_reserve(pool); // (the reserve belongs to the engine's own pool, not to the exportable twin)
+  stats().pages_mapped += (int64_t)(b.done.size() + b.kept.size());
+  if (b.pool->creations() > 0 && !imported && !exportable_) cold_start_reserve(b.pool); // (the reserve belongs to the engine's own pool, not to the exportable twin)
 }
 
 // Cold start: the first map calls of an allocator bring the reserve along (KVCACHED_PHYS_RESERVE_MB): pages
@@ -1595,7 +1670,7 @@ void KvAllocator::unmap_slots(const std::vector<Slot> &slots) {
         KVC_LOG(LOG_ERROR, "Page %zu is not mapped.", s.index);
         continue;
       }
-      s.region->mapped[s.index] = 0;
+      s.region->mapped[s.index] = Unbacked;
       stats().pages_unmapped++;
     }
     return;
@@ -1623,7 +1698,7 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
   // Pages of a multi-page extent may have been mapped together with their neighbours in one ioctl; taking some of them
   // out splits that mapping, and what is left of it must be rewritten (DrmVm::refresh_mappings_of) before the TLBs are
   // invalidated. An extent that loses ALL its mapped pages in this batch leaves nothing behind to rewrite.
-  ExtentPool *xpool = ctx->extents(ps, exportable_);
+  ExtentPool *xpool = u.pool = ctx->extents(ps, exportable_);
   KeyGroups<uint32_t> touched(slots.size()); // extent -> pieces of it that this batch takes back
   std::vector<std::pair<KvRegion *, size_t>> gone;
   gone.reserve(slots.size());
@@ -1641,7 +1716,7 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
       const uint8_t m = r.mapped[slots[i].index];
       // (a page ROCr mapped is ROCr's to unmap; our own pages of an extent pool are KFD buffers imported into DRM, all of them:
       // no need to ask DrmVm about each one. A slot listed twice: the second mention is logged as "not mapped" below)
-      if (r.rest_direct() && ((m == 1 && own_direct) || ((m == 1 || m == 2) && vmm_direct_bo(r.handle[slots[i].index]))))
+      if (r.rest_direct() && ((m == Own && own_direct) || ((m == Own || m == Imported) && vmm_direct_bo(r.handle[slots[i].index]))))
         if (scan.add(&r, slots[i].index)) cleared[i] = 2; // (2: and its extent is counted in `touched` with its run)
     }
     const std::vector<SlotRun> runs = scan.collect([](const KvRegion &r) { return r.rest_group(); });
@@ -1656,7 +1731,7 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
       if (own_direct)
         for (size_t k = run.first; k < run.first + run.count; ++k) {
           const phys_handle_t h = run.r->handle[k];
-          if (run.r->mapped[k] == 1 && is_piece(h)) ++touched.at(chunk_of(h));
+          if (run.r->mapped[k] == Own && is_piece(h)) ++touched.at(chunk_of(h));
         }
     }
   }
@@ -1668,7 +1743,7 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
     for (uint32_t i = 0; i < slots.size(); ++i) {
       KvRegion &r = *slots[i].region;
       const uint8_t m = r.mapped[slots[i].index];
-      if (!r.backfilled && !r.rest_direct() && ((m == 1 && own_direct) || ((m == 1 || m == 2) && vmm_direct_bo(r.handle[slots[i].index]))))
+      if (!r.backfilled && !r.rest_direct() && ((m == Own && own_direct) || ((m == Own || m == Imported) && vmm_direct_bo(r.handle[slots[i].index]))))
         if (scan.add(&r, slots[i].index)) cleared[i] = 1;
     }
     for (const SlotRun &run : scan.collect([](const KvRegion &) { return (size_t)-1; }, max_clear)) {
@@ -1680,7 +1755,7 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
   for (size_t si = 0; si < slots.size(); ++si) {
     const Slot &s = slots[si];
     KvRegion &r = *s.region;
-    if (r.mapped[s.index] != 1 && r.mapped[s.index] != 2) { // reference: log + skip (ftensor.cpp:124-127)
+    if (r.mapped[s.index] != Own && r.mapped[s.index] != Imported) { // reference: log + skip (ftensor.cpp:124-127)
       KVC_LOG(LOG_ERROR, "Page %zu is not mapped.", s.index);
       continue;
     }
@@ -1690,12 +1765,12 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
       vmm_unmap(va, ps, r.handle[s.index]);
       stats().t_unmap += now_ns() - t0;
     }
-    const bool own = r.mapped[s.index] == 1;
+    const bool own = r.mapped[s.index] == Own;
     if (own)
       u.own.push_back(Phys{r.handle[s.index], r.seq[s.index]});
     else
       u.imported.push_back(r.handle[s.index]);
-    r.mapped[s.index] = 0;
+    r.mapped[s.index] = Unbacked;
     gone.emplace_back(&r, s.index);
     ++u.n;
     if (own && own_direct && cleared[si] != 2 && is_piece(r.handle[s.index])) ++touched.at(chunk_of(r.handle[s.index])); // (a tagged handle of our own pool: a page of a multi-page extent; those of the runs above are counted already)
@@ -1719,6 +1794,7 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
     }
   }
   flush_run();
+  u.foreign = !u.imported.empty();
   sg.mark(13);
   if (!touched.items().empty() && !KVC_TEST_HOOK("SKIP_REMAINDER_REFRESH")) { // hook: prove the test has teeth
     for (auto &kv : touched.items()) {
@@ -1738,12 +1814,37 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
   sg.mark(15);
 }
 
+namespace {
+// Zero pages on their way back: the fill is queued (through the alias mappings of their buffers) BEFORE they are on
+// offer again, and whoever gets them next only waits for that ticket (GpuContext::scrub). `rows` == 0: `own` are single
+// pages of a plain pool; otherwise lanes of `rows` pages each - page (row, lane) of a buffer of k lanes sits at
+// (row x k + lane). Returns the scrub's ticket (0: nothing was queued).
+uint64_t scrub_on_the_way_back(GpuContext *ctx, ExtentPool *pool, const std::vector<Phys> &own, size_t rows, size_t ps) {
+  if (!options().zero_fill.load() || !options().scrub_on_release.load() || own.empty()) return 0;
+  std::vector<uint64_t> addrs;
+  if (!rows) {
+    if (!pool->multi_page()) return 0;
+    addrs.resize(own.size());
+    if (!pool->scrub_addresses(own.data(), own.size(), addrs.data())) return 0;
+  } else {
+    addrs.reserve(own.size() * rows);
+    for (const Phys &l : own)
+      if (const uint64_t tag = pool->tag_of(l.h)) {
+        const uint64_t ke = pages_of(l.h), j = piece_of(l.h);
+        for (size_t r = 0; r < rows; ++r) addrs.push_back(tag + ((uint64_t)r * ke + j) * ps);
+      }
+    if (addrs.empty()) return 0;
+  }
+  return ctx->scrub(addrs.data(), addrs.size(), ps);
+}
+} // namespace
+
 // TLB invalidation, then the handles go back to the pool / the driver. Touches no allocator state (the async
 // reclaimer calls it without mu_).
 void KvAllocator::unmap_finish(Unmapped &u, bool may_defer_shootdown) {
   if (!u.n) return;
   GpuContext *ctx = ctx_;
-  ExtentPool *pool = ctx->extents(u.page_size, exportable_);
+  ExtentPool *pool = u.pool;
   // Stale TLB entries still translate the unmapped VAs to the old physical pages. Who can be hurt by them?
   //   * a reader of the VA itself: only in compat mode is that legal (unbacked VA reads as zeros), so there the
   //     invalidation happens now;
@@ -1760,18 +1861,13 @@ void KvAllocator::unmap_finish(Unmapped &u, bool may_defer_shootdown) {
   //     (KVCACHED_ASYNC_SHOOTDOWN, on by default; one page id: free() 0.6 -> 0.2 ms).
   SegTimer sg;
   const int64_t trail_us = options().deferred_unmap_flush_us.load();
-  if (trail_us > 0 && u.any_backfilled && u.imported.empty() && may_defer_shootdown && !u.own.empty()) {
+  if (trail_us > 0 && u.any_backfilled && !u.foreign && may_defer_shootdown && !u.own.empty()) {
     // compat, relaxed (KVCACHED_UNMAP_INVALIDATION_US): the invalidation trails the call by at most trail_us - performed by
     // the context's thread, or absorbed by the next map batch's own. The pages wait for it un-scrubbed and un-offered.
     auto own = std::make_shared<std::vector<Phys>>(std::move(u.own));
-    const size_t ps = u.page_size;
-    ctx->park(u.epoch, own->size() * ps, [ctx, pool, own, ps]() {
-      uint64_t ticket = 0;
-      if (options().zero_fill.load() && options().scrub_on_release.load() && pool->multi_page()) {
-        std::vector<uint64_t> addrs(own->size());
-        if (pool->scrub_addresses(own->data(), own->size(), addrs.data())) ticket = ctx->scrub(addrs.data(), addrs.size(), ps);
-      }
-      pool->release_batch(own->data(), own->size(), ticket);
+    const size_t rows = u.rows, ps = u.page_size;
+    ctx->park(u.epoch, own->size() * pool->page_bytes(), [ctx, pool, own, rows, ps]() {
+      pool->release_batch(own->data(), own->size(), scrub_on_the_way_back(ctx, pool, *own, rows, ps));
     });
     ctx->request_async_flush(trail_us);
     sg.mark(16);
@@ -1779,7 +1875,7 @@ void KvAllocator::unmap_finish(Unmapped &u, bool may_defer_shootdown) {
     return;
   }
   const bool defer = options().defer_unmap_shootdown.load() || options().async_shootdown.load();
-  if (u.any_backfilled || !u.imported.empty() || !may_defer_shootdown || !defer) {
+  if (u.any_backfilled || u.foreign || !may_defer_shootdown || !defer) {
     // (starting it on the context's thread and overlapping the scrub launch and the pool with it was tried: the thread
     // hand-off costs what the overlap gains)
     ctx->ensure_flushed();
@@ -1792,13 +1888,7 @@ void KvAllocator::unmap_finish(Unmapped &u, bool may_defer_shootdown) {
   }
   sg.mark(16);
   const int64_t tr0 = now_ns();
-  // Zero the pages on their way back: the fill is queued (through the alias mappings of their buffers) BEFORE they are on
-  // offer again, and whoever gets them next only waits for that ticket (GpuContext::scrub).
-  uint64_t ticket = 0;
-  if (options().zero_fill.load() && options().scrub_on_release.load() && pool->multi_page() && !u.own.empty()) {
-    std::vector<uint64_t> addrs(u.own.size());
-    if (pool->scrub_addresses(u.own.data(), u.own.size(), addrs.data())) ticket = ctx->scrub(addrs.data(), addrs.size(), u.page_size);
-  }
+  const uint64_t ticket = scrub_on_the_way_back(ctx, pool, u.own, u.rows, u.page_size);
   sg.mark(17);
   pool->release_batch(u.own.data(), u.own.size(), ticket);
   sg.mark(18);
@@ -1869,7 +1959,7 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
     if (off < 0 || (size_t)off % ps != 0 || (size_t)off / ps >= ids_per_row_) return false;
     const size_t p = (size_t)off / ps;
     for (const Row &row : rows_) {
-      if (row.r->mapped[row.first + p] != 0) return false;
+      if (row.r->mapped[row.first + p] != Unbacked) return false;
       need_epoch = std::max(need_epoch, row.r->stale_epoch[row.first + p]);
     }
     if (!scan.add(rows_[0].r, rows_[0].first + p)) return false;
@@ -1878,7 +1968,6 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
   ctx->bind();
   ExtentPool *pool = lane_pool_;
   if (!ctx->primary_pool()) ctx->set_primary_pool(pool);
-  const bool cold = pool->creations() == 0;
   const bool fill = options().zero_fill.load() != 0;
   if (vmm_hip_registered()) // once per slot (a rest_direct region did it when it was made)
     for (size_t i = 0; i < n; ++i)
@@ -1913,14 +2002,8 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
         c.p = at;
         c.k = c.rows_done = 0;
         c.settled = false;
-        bool recycled = false;
         const int64_t t1 = now_ns();
-        c.k = pool->acquire_run(end - at, c.lane, &recycled, false);
-        if (!c.k && ctx->limbo_bytes()) { // pages of an earlier unmap wait for their invalidation: have it now rather than create
-          ctx->flush_limbo();
-          c.k = pool->acquire_run(end - at, c.lane, &recycled, false);
-        }
-        if (!c.k) c.k = pool->acquire_run(end - at, c.lane, &recycled, true);
+        c.k = acquire_pages(pool, end - at, c.lane, /*stolen=*/nullptr); // (a stolen page is not a lane)
         const int64_t t2 = now_ns();
         sg.mark(3);
         unsigned j0 = 0, ke = 1;
@@ -1960,7 +2043,7 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
             const size_t idx = rows_[r].first + at + j;
             reg.handle[idx] = c.lane[j].h;
             reg.seq[idx] = c.lane[j].seq;
-            reg.mapped[idx] = 4;
+            reg.mapped[idx] = Lane;
             if (fill && !clean) pending.push_back(reg.base + idx * ps);
           }
         }
@@ -1970,23 +2053,8 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
         sg.mark(5);
       }
     }
-    // nothing may reach the new pages through a stale translation of their own addresses: the remainders of what the
-    // REPLACEs split are rewritten (their page-table entries still carry the fragment of the whole), then the invalidation
-    const int64_t t_rw = now_ns();
-    if (prt_dirty && !KVC_TEST_HOOK("SKIP_PRT_REMAINDER_REFRESH") && !vm.refresh_prt_remainders())
-      throw GpuError("rewriting the remainders of split PRT mappings failed");
-    if (zx_dirty && !vm.refresh_mappings_of(zx_dirty, ps)) KVC_LOG(LOG_ERROR, "rewriting the remaining mappings of the zero extent failed");
-    stats().seg[20] += now_ns() - t_rw;
-    if (replaced) {
-      tlb_stale().store(true);
-      need_epoch = ctx->next_flush_epoch();
-    }
-    if (options().map_waits_for_all_flushes.load() || options().map_shootdown_always.load()) {
-      if (options().map_shootdown_always.load()) tlb_stale().store(true);
-      ctx->ensure_flushed();
-    } else {
-      ctx->ensure_flushed_through(need_epoch);
-    }
+    // (no flush happens between the REPLACEs of this path, so they are all noted here, once)
+    settle_batch(ctx, ps, prt_dirty, zx_dirty, need_epoch, replaced || options().map_shootdown_always.load() != 0);
     sg.mark(6);
     const int64_t ts = now_ns();
     for (size_t i = 0; i < pending.size(); i += kMaxPtrsPerLaunch) { // fresh memory, or pages that came back unscrubbed
@@ -1999,30 +2067,25 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
     stats().t_sync += now_ns() - ts;
     sg.mark(8);
   } catch (...) {
-    if (launched) (void)hipStreamSynchronize(ctx->stream());
-    for (auto it = done.rbegin(); it != done.rend(); ++it) {
-      for (size_t r = 0; r < it->rows_done; ++r) {
-        KvRegion &reg = *rows_[r].r;
-        if (reg.rest_direct())
-          for_rest_pieces(reg, rows_[r].first + it->p, it->k, [&](size_t first, size_t cnt) { (void)rest_replace(reg, first, cnt); });
-        else
-          (void)vmm_try_unmap(reg.base + (rows_[r].first + it->p) * ps, it->k * ps, it->lane[0].h);
+    roll_back(ctx, launched, [&]() {
+      for (auto it = done.rbegin(); it != done.rend(); ++it) {
+        for (size_t r = 0; r < it->rows_done; ++r) {
+          KvRegion &reg = *rows_[r].r;
+          if (reg.rest_direct())
+            for_rest_pieces(reg, rows_[r].first + it->p, it->k, [&](size_t first, size_t cnt) { (void)rest_replace(reg, first, cnt); });
+          else
+            (void)vmm_try_unmap(reg.base + (rows_[r].first + it->p) * ps, it->k * ps, it->lane[0].h);
+        }
+        if (it->settled)
+          for (size_t j = 0; j < it->k; ++j)
+            for (const Row &row : rows_) row.r->mapped[row.first + it->p + j] = Unbacked;
+        if (it->k) pool->release_batch(it->lane, it->k);
       }
-      if (it->settled)
-        for (size_t j = 0; j < it->k; ++j)
-          for (const Row &row : rows_) row.r->mapped[row.first + it->p + j] = 0;
-      if (it->k) pool->release_batch(it->lane, it->k);
-    }
-    (void)hipGetLastError();
-    try {
-      ctx->tlb_shootdown();
-    } catch (...) {
-    }
+    });
     throw;
   }
   stats().pages_mapped += (int64_t)(ids * R);
   if (prescrubbed) stats().pages_prescrubbed += (int64_t)prescrubbed;
-  (void)cold;
   if (pool->creations() > 0) cold_start_reserve(pool);
   return true;
 }
@@ -2034,8 +2097,8 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
   for (size_t i = 0; i < n; ++i) {
     const offset_t off = offsets[i];
     const bool valid = off >= 0 && (size_t)off % ps == 0 && (size_t)off / ps < ids_per_row_;
-    const uint8_t state = valid ? rows_[0].r->mapped[rows_[0].first + (size_t)off / ps] : 0;
-    if (state == 4 || state == 5) {
+    const uint8_t state = valid ? rows_[0].r->mapped[rows_[0].first + (size_t)off / ps] : Unbacked;
+    if (state == Lane || state == PeerLane) {
       if (!scan.add(rows_[0].r, rows_[0].first + (size_t)off / ps)) KVC_LOG(LOG_ERROR, "Page %zu is not mapped.", (size_t)off / ps); // named twice
     } else {
       others->push_back(off);
@@ -2047,10 +2110,12 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
   ExtentPool *pool = lane_pool_;
   const std::vector<SlotRun> runs = scan.collect();
   sg.mark(11);
-  std::vector<Phys> lanes;
+  Unmapped u; // own: the lanes that go home
+  u.pool = pool;
+  u.rows = R;
+  u.page_size = ps;
   std::vector<phys_handle_t> peers_buffers; // page ids that were backed by a peer's lane: its buffer is released once, after the invalidation
   KeyGroups<uint32_t> touched(n); // buffer -> lanes of it that this call takes back
-  bool any_backfilled = false;
   for (const SlotRun &run : runs) {
     const size_t p0 = run.first - rows_[0].first;
     for (size_t r = 0; r < R; ++r) {
@@ -2062,7 +2127,7 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
           if (rc != 0) throw GpuError(std::string("DRM_AMDGPU_GEM_VA replace (back to the rest state) failed: ") + strerror(rc < 0 ? -rc : rc));
           stats().seg[22]++;
         });
-        any_backfilled = any_backfilled || reg.backfilled;
+        u.any_backfilled = u.any_backfilled || reg.backfilled;
       } else {
         vmm_unmap_run(reg.base + (rows_[r].first + p0) * ps, run.count * ps);
         stats().seg[22]++;
@@ -2072,11 +2137,11 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
     for (size_t p = p0; p < p0 + run.count; ++p) {
       const size_t idx0 = rows_[0].first + p;
       const phys_handle_t h = rows_[0].r->handle[idx0];
-      if (rows_[0].r->mapped[idx0] == 5) {
+      if (rows_[0].r->mapped[idx0] == PeerLane) {
         peers_buffers.push_back(h);
         continue;
       }
-      lanes.push_back(Phys{h, rows_[0].r->seq[idx0]});
+      u.own.push_back(Phys{h, rows_[0].r->seq[idx0]});
       ++touched.at(chunk_of(h));
     }
   }
@@ -2084,7 +2149,7 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
   for (const SlotRun &run : runs)
     for (const Row &row : rows_) {
       const size_t first = row.first + (run.first - rows_[0].first);
-      std::fill(row.r->mapped.begin() + first, row.r->mapped.begin() + first + run.count, 0);
+      std::fill(row.r->mapped.begin() + first, row.r->mapped.begin() + first + run.count, Unbacked);
     }
   sg.mark(13);
   // Lanes that were backed together share one mapping per row; taking some of them out splits it, and what is left of it
@@ -2101,76 +2166,25 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
     if (any) tlb_stale().store(true);
   }
   sg.mark(14);
-  const uint64_t epoch = ctx->next_flush_epoch(); // every driver call that removed or rewrote a translation has returned
+  const uint64_t epoch = u.epoch = ctx->next_flush_epoch(); // every driver call that removed or rewrote a translation has returned
   for (const SlotRun &run : runs)
     for (const Row &row : rows_) {
       const size_t first = row.first + (run.first - rows_[0].first);
       std::fill(row.r->stale_epoch.begin() + first, row.r->stale_epoch.begin() + first + run.count, epoch);
     }
   sg.mark(15);
-  // the invalidation: inside the call where unbacked VA promises zeros (compat), behind it otherwise (see unmap_finish)
-  const size_t n_ids = lanes.size() + peers_buffers.size();
-  if (!peers_buffers.empty()) { // a peer's memory: no translation of it may survive the call
-    ctx->ensure_flushed();
-    for (auto h : peers_buffers) { // (one entry per page id: the buffer goes when the last page id it backs here has gone)
-      auto it = peer_refs_.find(h);
-      if (it != peer_refs_.end() && --it->second > 0) continue;
-      if (it != peer_refs_.end()) peer_refs_.erase(it);
-      if (!vmm_try_release(h)) KVC_LOG(LOG_ERROR, "releasing an imported buffer failed");
-    }
-    if (lanes.empty()) {
-      stats().pages_unmapped += (int64_t)(n_ids * R);
-      return n_ids;
-    }
+  // a peer's memory: no translation of it may survive the call (one entry per page id: the buffer goes - behind the
+  // invalidation - when the last page id it backs here has gone)
+  u.foreign = !peers_buffers.empty();
+  for (auto h : peers_buffers) {
+    auto it = peer_refs_.find(h);
+    if (it != peer_refs_.end() && --it->second > 0) continue;
+    if (it != peer_refs_.end()) peer_refs_.erase(it);
+    u.imported.push_back(h);
   }
-  const int64_t trail_us = options().deferred_unmap_flush_us.load();
-  if (trail_us > 0 && any_backfilled && peers_buffers.empty()) { // compat, relaxed: see unmap_finish
-    auto own = std::make_shared<std::vector<Phys>>(std::move(lanes));
-    ctx->park(epoch, own->size() * R * ps, [ctx, pool, own, R, ps]() {
-      uint64_t ticket = 0;
-      if (options().zero_fill.load() && options().scrub_on_release.load()) {
-        std::vector<uint64_t> addrs;
-        addrs.reserve(own->size() * R);
-        for (const Phys &l : *own)
-          if (const uint64_t tag = pool->tag_of(l.h)) {
-            const uint64_t ke = pages_of(l.h), j = piece_of(l.h);
-            for (size_t r = 0; r < R; ++r) addrs.push_back(tag + ((uint64_t)r * ke + j) * ps);
-          }
-        if (!addrs.empty()) ticket = ctx->scrub(addrs.data(), addrs.size(), ps);
-      }
-      pool->release_batch(own->data(), own->size(), ticket);
-    });
-    ctx->request_async_flush(trail_us);
-    sg.mark(16);
-    stats().pages_unmapped += (int64_t)(own->size() * R);
-    return own->size();
-  }
-  const bool defer = options().defer_unmap_shootdown.load() || options().async_shootdown.load();
-  if (any_backfilled || !defer)
-    ctx->ensure_flushed();
-  else if (options().defer_unmap_shootdown.load())
-    ctx->defer_tlb_shootdown();
-  else
-    ctx->request_async_flush();
-  sg.mark(16);
-  const int64_t tr0 = now_ns();
-  // zeroed on their way back, through the alias mapping of their buffer: page (row, lane) sits at (row x k + lane)
-  uint64_t ticket = 0;
-  if (options().zero_fill.load() && options().scrub_on_release.load()) {
-    std::vector<uint64_t> addrs;
-    addrs.reserve(lanes.size() * R);
-    for (const Phys &l : lanes)
-      if (const uint64_t tag = pool->tag_of(l.h)) {
-        const uint64_t ke = pages_of(l.h), j = piece_of(l.h);
-        for (size_t r = 0; r < R; ++r) addrs.push_back(tag + ((uint64_t)r * ke + j) * ps);
-      }
-    if (!addrs.empty()) ticket = ctx->scrub(addrs.data(), addrs.size(), ps);
-  }
-  sg.mark(17);
-  pool->release_batch(lanes.data(), lanes.size(), ticket);
-  sg.mark(18);
-  stats().t_release += now_ns() - tr0;
-  stats().pages_unmapped += (int64_t)(n_ids * R);
+  const size_t n_ids = u.own.size() + peers_buffers.size();
+  u.n = (int64_t)(n_ids * R);
+  unmap_finish(u, true); // the invalidation: inside the call where unbacked VA promises zeros (compat), behind it otherwise
   return n_ids;
 }
 
@@ -2238,7 +2252,7 @@ int KvAllocator::export_mapped_slots(const offset_t *offsets, size_t n, int *out
   if ((int64_t)slots.size() > cap) return (int)slots.size();
   ctx_->bind();
   for (auto &s : slots) // nothing is exported unless everything can be
-    if (s.region->mapped[s.index] != 1) throw InvalidError("export of a slot that is not backed by a local page");
+    if (s.region->mapped[s.index] != Own) throw InvalidError("export of a slot that is not backed by a local page");
   int k = 0;
   try {
     for (auto &s : slots) {
@@ -2266,7 +2280,7 @@ int KvAllocator::export_page_ids(const offset_t *offsets, size_t n, int *out_fds
   const size_t ps = rows_[0].r->page_size;
   for (size_t i = 0; i < n; ++i) { // nothing is exported unless everything can be
     const offset_t off = offsets[i];
-    if (off < 0 || (size_t)off % ps != 0 || (size_t)off / ps >= ids_per_row_ || rows_[0].r->mapped[rows_[0].first + (size_t)off / ps] != 4)
+    if (off < 0 || (size_t)off % ps != 0 || (size_t)off / ps >= ids_per_row_ || rows_[0].r->mapped[rows_[0].first + (size_t)off / ps] != Lane)
       throw InvalidError("export of a page id that is not backed by a lane of this process");
   }
   ctx_->bind();
@@ -2314,7 +2328,7 @@ bool KvAllocator::map_imported_page_ids(const offset_t *offsets, size_t n, const
       throw InvalidError("import of a page id: (fd " + std::to_string(b) + ", lane " + std::to_string(j) + " of " + std::to_string(k) + ") names no lane of the buffers that came along");
     ids[i] = Id{(size_t)off / ps, (uint64_t)b, (uint64_t)k, (uint64_t)j};
     for (const Row &row : rows_)
-      if (row.r->mapped[row.first + ids[i].p] != 0) throw InvalidError("import into a page id that is backed already");
+      if (row.r->mapped[row.first + ids[i].p] != Unbacked) throw InvalidError("import into a page id that is backed already");
   }
   std::sort(ids.begin(), ids.end(), [](const Id &a, const Id &b) { return a.p < b.p; });
   for (size_t i = 1; i < n; ++i)
@@ -2376,37 +2390,28 @@ bool KvAllocator::map_imported_page_ids(const offset_t *offsets, size_t n, const
         for (size_t c = 0; c < cnt; ++c) {
           row.r->handle[row.first + first.p + c] = d.h;
           row.r->seq[row.first + first.p + c] = 0;
-          row.r->mapped[row.first + first.p + c] = 5;
+          row.r->mapped[row.first + first.p + c] = PeerLane;
         }
       d.settled = true;
       stats().seg[21] += (int64_t)R;
       i += cnt;
     }
-    if (prt_dirty && !vm.refresh_prt_remainders()) throw GpuError("rewriting the remainders of split PRT mappings failed");
-    if (zx_dirty && !vm.refresh_mappings_of(zx_dirty, ps)) KVC_LOG(LOG_ERROR, "rewriting the remaining mappings of the zero extent failed");
-    if (replaced) {
-      tlb_stale().store(true);
-      need_epoch = ctx->next_flush_epoch();
-    }
-    ctx->ensure_flushed_through(need_epoch);
+    settle_batch(ctx, ps, prt_dirty, zx_dirty, need_epoch, replaced);
   } catch (...) {
-    for (auto it = done.rbegin(); it != done.rend(); ++it) {
-      for (size_t r = 0; r < it->rows_done; ++r) {
-        KvRegion &reg = *rows_[r].r;
-        if (reg.rest_direct())
-          for_rest_pieces(reg, rows_[r].first + it->p, it->cnt, [&](size_t f0, size_t c) { (void)rest_replace(reg, f0, c); });
-        else
-          (void)vm.clear(reg.base + (rows_[r].first + it->p) * ps, it->cnt * ps);
+    roll_back(ctx, /*launched=*/false, [&]() {
+      for (auto it = done.rbegin(); it != done.rend(); ++it) {
+        for (size_t r = 0; r < it->rows_done; ++r) {
+          KvRegion &reg = *rows_[r].r;
+          if (reg.rest_direct())
+            for_rest_pieces(reg, rows_[r].first + it->p, it->cnt, [&](size_t f0, size_t c) { (void)rest_replace(reg, f0, c); });
+          else
+            (void)vm.clear(reg.base + (rows_[r].first + it->p) * ps, it->cnt * ps);
+        }
+        if (it->settled)
+          for (const Row &row : rows_)
+            for (size_t c = 0; c < it->cnt; ++c) row.r->mapped[row.first + it->p + c] = Unbacked;
       }
-      if (it->settled)
-        for (const Row &row : rows_)
-          for (size_t c = 0; c < it->cnt; ++c) row.r->mapped[row.first + it->p + c] = 0;
-    }
-    (void)hipGetLastError();
-    try {
-      ctx->tlb_shootdown();
-    } catch (...) {
-    }
+    });
     for (auto h : bufs)
       if (h) (void)vmm_try_release(h);
     throw;
