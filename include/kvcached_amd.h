@@ -293,7 +293,8 @@ int64_t kvc_get_region_bases(int64_t group_id, void **out, int64_t cap);
  *                           last_loc[r]+1; out[bs]                              (patches.py:245-276 + alloc_decode_kernel)
  * kvc_unique_block_ids      BLOCKING. Distinct blocks of n token indices, ascending = torch.unique(idx // tpb)
  *                           (patches.py:278-288), into the host array out_host[cap]; returns the count (copied only
- *                           if it fits) or KVC_E_INVALID if an index is outside [0, num_blocks*tpb). */
+ *                           if it fits) or KVC_E_INVALID if an index is outside [0, num_blocks*tpb), or if
+ *                           num_blocks is above 2^32 (refused before anything is allocated or launched). */
 int kvc_expand_block_ids(const int64_t *block_ids, size_t n, int64_t tokens_per_block, int64_t *out_dev, void *stream);
 int kvc_alloc_extend_indices(const int64_t *prefix_lens_dev, const int64_t *seq_lens_dev, const int64_t *last_loc_dev,
                              size_t bs, const int64_t *new_block_ids, size_t n_new, int64_t tokens_per_block,

@@ -664,6 +664,8 @@ int64_t GpuContext::unique_block_ids(const int64_t *idx, size_t n, int64_t tpb, 
   // (s == NULL is the device's default stream here - what torch.cuda.current_stream() is unless the caller switched: these
   // kernels consume and produce tensors of the caller's stream, the library's own non-blocking stream would race with them)
   if (tpb <= 0 || n_blocks <= 0) throw InvalidError("tokens_per_block and num_blocks must be positive");
+  if (n_blocks > kMaxUniqueBlocks) // before the bitmap is sized for it: the kernels hold a block number in 32 bits
+    throw InvalidError("num_blocks " + std::to_string(n_blocks) + " is above the 2^32 blocks unique_block_ids can tell apart");
   std::lock_guard<std::mutex> g(uniq_mu_);
   const size_t words = ((size_t)n_blocks + 31) / 32;
   if (words > uniq_words_) {

@@ -153,11 +153,12 @@ __global__ __launch_bounds__(256) void mark_blocks_kernel(const int64_t *__restr
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= n) return;
   const int64_t v = idx[t];
-  if (v < 0 || v >= n_blocks * tpb) {
+  const int64_t blk = v / tpb; // (compared as a block number: n_blocks * tpb need not fit 64 bits)
+  if (v < 0 || blk >= n_blocks) {
     atomicAdd(&hdr->bad, 1u);
     return;
   }
-  const unsigned b = (unsigned)(v / tpb), w = b >> 5;
+  const unsigned b = (unsigned)blk, w = b >> 5; // blk < n_blocks <= kMaxUniqueBlocks = 2^32: nothing is cut off
   const unsigned bit = 1u << (b & 31u);
   if (!(__hip_atomic_load(&bitmap[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit)) {
     atomicOr(&bitmap[w], bit);
@@ -258,7 +259,7 @@ hipError_t launch_alloc_decode(const int64_t *ids_host, const int64_t *ids_dev, 
 
 hipError_t launch_unique_block_ids(const int64_t *idx, size_t n, int64_t tpb, int64_t n_blocks, unsigned *bitmap,
                                    void *header, int64_t *result, size_t cap, hipStream_t stream) {
-  if (tpb <= 0 || n_blocks <= 0 || n_blocks > 0x7fffffffll * 32) return hipErrorInvalidValue;
+  if (tpb <= 0 || n_blocks <= 0 || n_blocks > kMaxUniqueBlocks) return hipErrorInvalidValue;
   const size_t grid = (n + 255) / 256;
   if (grid > 0x7fffffffull) return hipErrorInvalidValue;
   if (n) mark_blocks_kernel<<<dim3((unsigned)grid), dim3(256), 0, stream>>>(idx, n, tpb, n_blocks, bitmap, (UniqueHeader *)header);

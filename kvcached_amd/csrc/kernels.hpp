@@ -55,7 +55,9 @@ hipError_t launch_alloc_extend(const int64_t *ids_host, const int64_t *ids_dev, 
 hipError_t launch_alloc_decode(const int64_t *ids_host, const int64_t *ids_dev, size_t n_ids, const int64_t *seq_lens,
                                const int64_t *last_loc, size_t bs, int64_t tpb, int64_t *out, hipStream_t stream);
 // result[0] = number of distinct blocks (or -(number of out-of-range indices)), result[1..] = ascending block ids.
+// n_blocks <= kMaxUniqueBlocks: the kernels carry a block number in 32 bits (bitmap word = block >> 5, bit = block & 31).
 // `bitmap` (>= ceil(n_blocks/32) zeroed words) and `header` (16 bytes {0xffffffff,0,0,0}) are left in that state.
+static constexpr int64_t kMaxUniqueBlocks = 1ll << 32;
 hipError_t launch_unique_block_ids(const int64_t *idx, size_t n, int64_t tpb, int64_t n_blocks, unsigned *bitmap,
                                    void *header, int64_t *result, size_t cap, hipStream_t stream);
 

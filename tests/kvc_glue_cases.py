@@ -5,9 +5,10 @@ import numpy as np
 
 
 def extend_case(seed: int, bs: int, tpb: int, max_prefix: int, max_extend: int, n_blocks: int = 1 << 20,
-                aligned_prefix: bool = False, zero_extend_every: int = 0):
+                aligned_prefix: bool = False, zero_extend_every: int = 0, id_base: int = 0):
     """A consistent alloc_extend input: each request owns distinct blocks for its prefix; last_loc is the slot of
-    its last prefix token (-1 when the prefix is empty, as SGLang passes it)."""
+    its last prefix token (-1 when the prefix is empty, as SGLang passes it). `id_base` is added to every drawn block id
+    (token indices of 2^31, 2^32 and beyond; the default leaves the cases as they always were)."""
     rng = np.random.default_rng(seed)
     pre = rng.integers(0, max_prefix + 1, size=bs)
     if aligned_prefix:
@@ -18,7 +19,7 @@ def extend_case(seed: int, bs: int, tpb: int, max_prefix: int, max_extend: int, 
     seq = pre + ext
     pre_blocks = (pre + tpb - 1) // tpb
     new_blocks = (seq + tpb - 1) // tpb - pre_blocks
-    ids = rng.permutation(n_blocks)[: int(pre_blocks.sum() + new_blocks.sum())].astype(np.int64)
+    ids = rng.permutation(n_blocks)[: int(pre_blocks.sum() + new_blocks.sum())].astype(np.int64) + np.int64(id_base)
     owned, k = [], 0
     for n in pre_blocks:
         owned.append(ids[k:k + n])
@@ -29,7 +30,8 @@ def extend_case(seed: int, bs: int, tpb: int, max_prefix: int, max_extend: int, 
                 free_pages=free_pages, tpb=tpb, owned=owned, extend_num_tokens=int(ext.sum()))
 
 
-def decode_case(seed: int, bs: int, tpb: int, max_len: int, n_blocks: int = 1 << 20, force_boundary_every: int = 0):
+def decode_case(seed: int, bs: int, tpb: int, max_len: int, n_blocks: int = 1 << 20, force_boundary_every: int = 0,
+                id_base: int = 0):
     rng = np.random.default_rng(seed)
     seq = rng.integers(1, max_len + 1, size=bs)
     if force_boundary_every:
@@ -37,7 +39,7 @@ def decode_case(seed: int, bs: int, tpb: int, max_len: int, n_blocks: int = 1 <<
     pre = seq - 1
     pre_blocks = (pre + tpb - 1) // tpb
     need = (seq + tpb - 1) // tpb - pre_blocks
-    ids = rng.permutation(n_blocks)[: int(pre_blocks.sum() + need.sum())].astype(np.int64)
+    ids = rng.permutation(n_blocks)[: int(pre_blocks.sum() + need.sum())].astype(np.int64) + np.int64(id_base)
     owned, k = [], 0
     for n in pre_blocks:
         owned.append(ids[k:k + n])
@@ -67,6 +69,26 @@ def check_extend_invariants(case, out):
     assert len(set(used_new)) == len(used_new)
 
 
+def case_id(c) -> str:
+    """pytest id of a case: the cases without an id_base keep the ids they always had."""
+    return f"s{c['seed']}_bs{c['bs']}_t{c['tpb']}" + (f"_base{c['id_base']}" if c.get("id_base") else "")
+
+
+def wide_id_bases(tpb: int):
+    """Block id bases whose token indices (id * tpb + j) straddle 2^31, straddle 2^32, and lie at 2^40 * tpb."""
+    return [(1 << 31) // tpb - 3, (1 << 32) // tpb - 3, 1 << 40]
+
+
+# Small batches and 48 candidate blocks (the drawn ids are base + part of a permutation of 0..47, the line lies at base + 3);
+# the seeds are the first ones for which the new blocks' token indices lie on both sides of the line (and, for extend, the
+# prefix blocks' too): test_sglang_glue.py asserts that they do. The point of these cases is the width of the values.
+_WIDE_EXTEND_SEEDS = {1: (101, 101, 100), 16: (111, 111, 100), 48: (105, 105, 100)}
+_WIDE_DECODE_SEEDS = {1: (202, 202, 200), 16: (200, 200, 200), 48: (200, 200, 200)}
+WIDE_EXTEND_CASES = [dict(seed=_WIDE_EXTEND_SEEDS[tpb][i], bs=6, tpb=tpb, max_prefix=2 * tpb, max_extend=2 * tpb + 3, n_blocks=48,
+                          id_base=base) for tpb in (1, 16, 48) for i, base in enumerate(wide_id_bases(tpb))]
+WIDE_DECODE_CASES = [dict(seed=_WIDE_DECODE_SEEDS[tpb][i], bs=12, tpb=tpb, max_len=2 * tpb + 2, n_blocks=48, force_boundary_every=2,
+                          id_base=base) for tpb in (1, 16, 48) for i, base in enumerate(wide_id_bases(tpb))]
+
 EXTEND_CASES = [
     dict(seed=1, bs=1, tpb=16, max_prefix=0, max_extend=40),
     dict(seed=2, bs=7, tpb=16, max_prefix=100, max_extend=100),
@@ -74,10 +96,10 @@ EXTEND_CASES = [
     dict(seed=4, bs=33, tpb=1, max_prefix=20, max_extend=20),
     dict(seed=5, bs=50, tpb=3, max_prefix=40, max_extend=40, zero_extend_every=7),
     dict(seed=6, bs=300, tpb=64, max_prefix=500, max_extend=300),
-]
+] + WIDE_EXTEND_CASES
 DECODE_CASES = [
     dict(seed=1, bs=1, tpb=16, max_len=100),
     dict(seed=2, bs=257, tpb=16, max_len=1000, force_boundary_every=5),
     dict(seed=3, bs=64, tpb=1, max_len=50),
     dict(seed=4, bs=1000, tpb=3, max_len=200),
-]
+] + WIDE_DECODE_CASES

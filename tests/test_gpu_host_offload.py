@@ -86,6 +86,19 @@ BB_MATRIX = [16, 2064, 18 * 1024, 32 * 1024, 48 * 1024]
 @pytest.mark.parametrize("n_regions", [1, 2, 64])
 @pytest.mark.parametrize("bb", BB_MATRIX)
 def test_kernels_copy_blocks_byte_for_byte(lib, n_regions, bb):
+    _copy_blocks_byte_for_byte(lib, n_regions, bb)
+
+
+# Blocks of the contiguous layout (block_mem_size * layers * kv): 2 MiB for Llama-3-8B (128 tiles of 16 KiB), 497 664 B for the
+# 27-layer MLA geometry (30 full tiles and a ragged 6 KiB one). One and two regions only: _regions backs 3 * max(ns) + 3 blocks
+# per region, which at 64 regions would be 14 GiB of HBM for no extra coverage.
+@pytest.mark.parametrize("n_regions", [1, 2])
+@pytest.mark.parametrize("bb", [497664, 2 * MiB])
+def test_kernels_copy_blocks_of_the_contiguous_layout(lib, n_regions, bb):
+    _copy_blocks_byte_for_byte(lib, n_regions, bb)
+
+
+def _copy_blocks_byte_for_byte(lib, n_regions, bb):
     ops, capi = lib
     ns = [n for n in N_MATRIX if n <= 37 or n * n_regions * bb <= 256 * MiB]   # 64 regions x 1024 large blocks: > 1 GiB images
     views = _regions(ops, capi, n_regions, (3 * max(ns) + 3) * bb)

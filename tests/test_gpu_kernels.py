@@ -114,6 +114,8 @@ def _oracle_compact(lib, hosts, src, dst, block_bytes):
     (1040, 1000, 5, 449, 5),         # ragged inside the first piece; more moves than one launch (448)
     (32 * KiB, 64, 130, 3, 6),       # more regions than one launch (128)
     (32 * KiB, 64, 2, 0, 7),         # empty move list
+    (2 * MiB, 24, 2, 5, 8),          # a block of the contiguous layout, Llama-3-8B: 64 tiles of 32 KiB
+    (497664, 40, 2, 9, 9),           # the same for the 27-layer MLA geometry: 15 full 32 KiB tiles and a ragged 6 KiB one
 ])
 def test_compact_blocks_matches_oracle(capi, oracle_lib, variant, block_bytes, n_blocks, n_regions, n_moves, seed):
     rng = np.random.default_rng(seed)
@@ -164,3 +166,12 @@ def test_compact_blocks_rejects_bad_arguments(capi):
         capi.compact_blocks([dev.data_ptr()], [-1], [1], 32)     # negative id
     with pytest.raises(ValueError):
         capi.compact_blocks([dev.data_ptr()], [0, 1], [2], 32)
+    dev.copy_(torch.arange(1 * MiB, dtype=torch.int64, device="cuda:0").to(torch.uint8))
+    before = dev.clone()
+    torch.cuda.synchronize()
+    with pytest.raises(capi.KvcError):
+        capi.compact_blocks([dev.data_ptr()], [0], [1], 1 << 31)   # a multiple of 16 above what the launcher's 32-bit sizes hold
+    torch.cuda.synchronize()
+    assert torch.equal(dev, before)
+    capi.compact_blocks([dev.data_ptr()], [3], [1], 32)          # and the next ordinary call works
+    assert torch.equal(dev[32:64], before[96:128]) and torch.equal(dev[64:], before[64:]) and torch.equal(dev[:32], before[:32])

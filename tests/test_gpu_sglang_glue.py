@@ -37,6 +37,13 @@ def test_expand_block_ids(gpu_lib, n, tpb):
     got = expand_block_ids([int(x) for x in ids], tpb, DEV)
     torch.cuda.synchronize()
     assert got.dtype == torch.int64 and np.array_equal(got.cpu().numpy(), O.expand_block_ids(ids, tpb))
+    # the same ids moved up: token indices that straddle 2^31 and 2^32, and block ids of 2^40; compared as int64
+    small = ids % (1 << 12)
+    for base in G.wide_id_bases(tpb):
+        got = expand_block_ids([int(x) + base for x in small], tpb, DEV)
+        torch.cuda.synchronize()
+        want = O.expand_block_ids(small + base, tpb)
+        assert got.dtype == torch.int64 and want.dtype == np.int64 and np.array_equal(got.cpu().numpy(), want), base
 
 
 EXTEND_GPU_CASES = G.EXTEND_CASES + [
@@ -47,7 +54,7 @@ EXTEND_GPU_CASES = G.EXTEND_CASES + [
 ]
 
 
-@pytest.mark.parametrize("cfg", EXTEND_GPU_CASES, ids=lambda c: f"s{c['seed']}_bs{c['bs']}_t{c['tpb']}")
+@pytest.mark.parametrize("cfg", EXTEND_GPU_CASES, ids=G.case_id)
 def test_alloc_extend_indices(gpu_lib, cfg):
     from kvcached_amd.integration.sglang.allocators import alloc_extend_indices
     case = G.extend_case(**cfg)
@@ -86,7 +93,7 @@ DECODE_GPU_CASES = G.DECODE_CASES + [
 ]
 
 
-@pytest.mark.parametrize("cfg", DECODE_GPU_CASES, ids=lambda c: f"s{c['seed']}_bs{c['bs']}_t{c['tpb']}")
+@pytest.mark.parametrize("cfg", DECODE_GPU_CASES, ids=G.case_id)
 def test_alloc_decode_indices(gpu_lib, cfg):
     from kvcached_amd.integration.sglang.allocators import alloc_decode_indices
     case = G.decode_case(**cfg)
@@ -97,17 +104,42 @@ def test_alloc_decode_indices(gpu_lib, cfg):
 
 
 @pytest.mark.parametrize("n,tpb,n_blocks", [(1, 16, 10), (3000, 16, 5000), (100000, 16, 200000), (5000, 1, 1 << 20),
-                                             (4096, 48, 3_000_000)])
+                                             (4096, 48, 3_000_000),
+                                             (4096, 64, 1 << 27)])   # indices up to 2^33 - 1, a 16 MiB bitmap
 def test_unique_block_ids(gpu_lib, n, tpb, n_blocks):
     from kvcached_amd.integration.sglang.allocators import unique_block_ids
     rng = np.random.default_rng(n + tpb)
     idx = rng.integers(0, n_blocks * tpb, size=n)
     idx[0], idx[-1] = 0, n_blocks * tpb - 1                     # first and last block
+    lines = [v for v in ((1 << 31) - 1, 1 << 31, (1 << 32) - 1, 1 << 32) if v < n_blocks * tpb]
+    idx[1:1 + len(lines)] = lines                               # both sides of 2^31 and 2^32 where the pool reaches them
+    assert len(lines) == (4 if n_blocks == 1 << 27 else 0) and idx.dtype == np.int64
     got = unique_block_ids(dev(idx), tpb, n_blocks)
     assert got == O.unique_block_ids(idx, tpb).tolist()
     # the scratch bitmap is clean again: a second, different query is not polluted by the first
     idx2 = rng.integers(0, min(n_blocks, 50) * tpb, size=200)
     assert unique_block_ids(dev(idx2), tpb, n_blocks) == O.unique_block_ids(idx2, tpb).tolist()
+
+
+def test_unique_block_ids_beyond_2_to_32_blocks(gpu_lib):
+    """num_blocks above 2^32 is more than the bitmap kernels' 32-bit block number holds: the call is refused before anything
+    is launched (or, were it ever supported, answers exactly) - it must never report a block that no index fell into. Before
+    the limit was put where the kernel's is, this returned [5, 4095]: both far indices folded down by 2^32."""
+    from kvcached_amd import capi
+    from kvcached_amd.integration.sglang.allocators import unique_block_ids
+    n_blocks = (1 << 32) + 4096
+    idx = [5, (1 << 32) + 5, (1 << 32) + 4095]
+    launches = capi.get_stats()["index_launches"]
+    try:
+        got = unique_block_ids(dev(idx), 1, n_blocks)
+    except (capi.KvcError, RuntimeError) as e:
+        print("refused:", e)
+        assert capi.get_stats()["index_launches"] == launches   # before anything was launched
+    else:
+        print("answered:", got)
+        assert got == idx
+    # and the next ordinary query is still correct
+    assert unique_block_ids(dev([33, 1, 17, 34]), 16, 100) == [0, 1, 2]
 
 
 def test_unique_block_ids_rejects_out_of_range_and_recovers(gpu_lib):

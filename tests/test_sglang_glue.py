@@ -21,6 +21,15 @@ def test_expand_matches_the_reference_expression(n, tpb):
     page_ids = torch.tensor(ids, dtype=torch.int64)
     want = (page_ids[:, None] * tpb + torch.arange(tpb)).reshape(-1)       # the reference's expression
     assert np.array_equal(O.expand_block_ids(ids, tpb), want.numpy())
+    # the same ids moved up: token indices that straddle 2^31 and 2^32, and block ids of 2^40; compared as int64
+    for base in G.wide_id_bases(tpb):
+        wide = ids % (1 << 12) + base
+        page_ids = torch.tensor(wide, dtype=torch.int64)
+        want = (page_ids[:, None] * tpb + torch.arange(tpb)).reshape(-1)
+        got = O.expand_block_ids(wide, tpb)
+        assert got.dtype == np.int64 and want.dtype == torch.int64 and np.array_equal(got, want.numpy())
+        if n:
+            assert int(got.max()) == (int(wide.max()) + 1) * tpb - 1      # in Python ints: nothing wrapped on either side
 
 
 @pytest.mark.parametrize("tpb", [1, 16, 48])
@@ -30,7 +39,7 @@ def test_unique_matches_the_reference_expression(tpb):
     assert np.array_equal(O.unique_block_ids(idx, tpb), want.numpy())
 
 
-@pytest.mark.parametrize("cfg", G.EXTEND_CASES, ids=lambda c: f"s{c['seed']}_bs{c['bs']}_t{c['tpb']}")
+@pytest.mark.parametrize("cfg", G.EXTEND_CASES, ids=G.case_id)
 def test_oracle_alloc_extend_invariants(cfg):
     case = G.extend_case(**cfg)
     out = O.alloc_extend(case["prefix_lens"], case["seq_lens"], case["last_loc"], case["free_pages"], case["tpb"])
@@ -39,13 +48,58 @@ def test_oracle_alloc_extend_invariants(cfg):
     assert O.get_num_new_pages(case["seq_lens"], case["tpb"], case["prefix_lens"]) == len(case["free_pages"])
 
 
-@pytest.mark.parametrize("cfg", G.DECODE_CASES, ids=lambda c: f"s{c['seed']}_bs{c['bs']}_t{c['tpb']}")
+@pytest.mark.parametrize("cfg", G.DECODE_CASES, ids=G.case_id)
 def test_oracle_alloc_decode_is_a_one_token_extend(cfg):
     case = G.decode_case(**cfg)
     out = O.alloc_decode(case["seq_lens"], case["last_loc"], case["free_pages"], case["tpb"])
     ext = O.alloc_extend(case["seq_lens"] - 1, case["seq_lens"], case["last_loc"], case["free_pages"], case["tpb"])
     assert np.array_equal(out, ext)
     assert O.get_num_new_pages(case["seq_lens"], case["tpb"], decode=True) == len(case["free_pages"])
+
+
+def test_id_base_zero_leaves_the_cases_as_they_were():
+    for cfg in (c for c in G.EXTEND_CASES if "id_base" not in c):
+        a, b = G.extend_case(**cfg), G.extend_case(**cfg, id_base=0)
+        assert a.keys() == b.keys() and "id_base" not in cfg
+        for k in a:
+            if k == "owned":
+                assert all(np.array_equal(x, y) and x.dtype == y.dtype for x, y in zip(a[k], b[k]))
+            elif isinstance(a[k], np.ndarray):
+                assert np.array_equal(a[k], b[k]) and a[k].dtype == b[k].dtype
+            else:
+                assert a[k] == b[k]
+    # the same draw with a base is the same case, every block id moved by the base
+    cfg = G.EXTEND_CASES[1]
+    a, b = G.extend_case(**cfg), G.extend_case(**cfg, id_base=1 << 40)
+    assert np.array_equal(a["free_pages"] + (1 << 40), b["free_pages"]) and np.array_equal(a["seq_lens"], b["seq_lens"])
+    assert np.array_equal(np.where(a["last_loc"] < 0, -1, a["last_loc"] + (cfg["tpb"] << 40)), b["last_loc"])
+    for cfg in (c for c in G.DECODE_CASES if "id_base" not in c):
+        a, b = G.decode_case(**cfg), G.decode_case(**cfg, id_base=0)
+        assert all(np.array_equal(a[k], b[k]) for k in ("seq_lens", "last_loc", "free_pages")) and a["tpb"] == b["tpb"]
+        assert all(np.array_equal(x, y) for x, y in zip(a["owned"], b["owned"]))
+
+
+def test_wide_cases_lie_on_both_sides_of_their_line():
+    """The cases with an id_base are in the lists, and their token indices do what they are there for: straddle 2^31 or 2^32
+    (bases next to a line) or exceed 2^40."""
+    assert all(c in G.EXTEND_CASES for c in G.WIDE_EXTEND_CASES) and all(c in G.DECODE_CASES for c in G.WIDE_DECODE_CASES)
+    assert len(G.WIDE_EXTEND_CASES) == len(G.WIDE_DECODE_CASES) == 9
+
+    def check(ids, tpb, base):
+        lo, hi = ids * tpb, ids * tpb + tpb - 1
+        assert len(ids) >= 3 and ids.dtype == np.int64
+        if base == 1 << 40:
+            assert (lo >= (1 << 40)).all()
+        else:
+            line = min((1 << 31, 1 << 32), key=lambda x: abs(x - base * tpb))
+            assert (lo < line).any() and (hi >= line).any(), (tpb, base)
+
+    for cfg in G.WIDE_EXTEND_CASES:
+        case = G.extend_case(**cfg)
+        check(case["free_pages"], cfg["tpb"], cfg["id_base"])
+        check(np.concatenate(case["owned"]), cfg["tpb"], cfg["id_base"])
+    for cfg in G.WIDE_DECODE_CASES:
+        check(G.decode_case(**cfg)["free_pages"], cfg["tpb"], cfg["id_base"])
 
 
 def test_num_new_pages_host_helper():
