@@ -14,6 +14,7 @@ import time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 KiB = 1 << 10
+# one string per KVC_OPT_COMPACT_VARIANT number; kCompactVariants in kvcached_amd/csrc/kernels.hip is the source (recorded .jsonl files are keyed by these strings)
 VARIANTS = ["default (= lds+nt, 32 KiB tiles, an eighth of the pairs per XCD)", "reg+xcd+nt", "lds", "reg", "lds+xcd", "reg+xcd", "lds+xcd+nt, 32 KiB tiles", "reg+xcd+nt, 32 KiB tiles", "lds+xcd+nt, 16 KiB tiles (default until r03)", "lds+nt, 32 KiB tiles, an eighth of the pairs per XCD", "reg+nt, 32 KiB tiles, an eighth of the pairs per XCD", "lds+nt, 32 KiB tiles, an eighth of the pairs per XCD, XCDs out of step"]
 GEOMETRIES = ((2048 * KiB, 1, 2048, 1024),    # the ceiling: ONE region, 2 MiB blocks i -> i + 1024, i.e. a contiguous 2 GiB -> 2 GiB copy through the same kernel
               (32 * KiB, 64, 4096, 2048),     # Llama-3-8B: 32 layers x K/V regions, 32 KiB blocks

@@ -587,10 +587,7 @@ void GpuContext::copy_blocks_host(bool to_host, void *const *bases, size_t n_reg
     for (size_t i = 0; i < n; i += kMaxIdsPerLaunch) {
       const int ni = (int)std::min<size_t>(kMaxIdsPerLaunch, n - i);
       char *h = static_cast<char *>(host) + i * n_regions * block_bytes; // row i of the image
-      if (to_host)
-        HIP_CHECK(launch_copy_blocks_to_host(bases + r, nr, (int)r, (int)n_regions, ids + i, ni, block_bytes, h, s));
-      else
-        HIP_CHECK(launch_copy_blocks_from_host(bases + r, nr, (int)r, (int)n_regions, ids + i, ni, block_bytes, h, s));
+      HIP_CHECK(launch_copy_blocks_host(to_host, bases + r, nr, (int)r, (int)n_regions, ids + i, ni, block_bytes, h, s));
     }
   }
 }

@@ -18,26 +18,23 @@ static constexpr int kMaxMovesPerLaunch = 448; // 448 x 16 B + 128 x 8 B = 8 KiB
 static constexpr int kMaxIdsPerLaunch = 1024; // block ids one index-kernel launch carries in its kernarg (8 KiB)
 
 // Zero `n` pages of `page_bytes` each (n <= kMaxPtrsPerLaunch). Asynchronous on `stream`.
-// variant: 0 = default; others are tuning variants kept for A/B runs.
+// variant: 0 = default; the others are tuning variants kept for A/B runs (kFillVariants in kernels.hip is the list).
 hipError_t launch_zero_fill_pages(void *const *pages, int n, size_t page_bytes, hipStream_t stream, int variant = 0);
 
 // Copy blocks inside each region: for r < n_regions, m < n_moves:
 //   bases[r] + dst[m]*block_bytes  <-  bases[r] + src[m]*block_bytes
-// n_regions <= kMaxRegionsPerLaunch, n_moves <= kMaxMovesPerLaunch. variant 0 (= 9) = LDS-staged
-// (LDS-DMA in, ds_read_b128 + global_store out), a contiguous eighth of the (region, move) pairs per XCD, non-temporal accesses,
-// 32 KiB tiles; 10 = the same register-staged; 6 / 7 = LDS / register-staged with every eighth pair per XCD (the default of most of round 3); 8 and 1 = LDS / register-staged with 16 KiB tiles (8: the default until round 3); 2/3 = LDS/register-staged
-// with the plain interleaved placement and temporal accesses; 4/5 = LDS/register-staged XCD-aware with temporal accesses (A/B runs).
+// n_regions <= kMaxRegionsPerLaunch, n_moves <= kMaxMovesPerLaunch. variant: 0 = default; the others are tuning variants kept
+// for A/B runs (kCompactVariants in kernels.hip is the list: staging, tile, nt, placement of each).
 hipError_t launch_compact_blocks(void *const *bases, int n_regions, const int64_t *src, const int64_t *dst, int n_moves,
                                  size_t block_bytes, hipStream_t stream, int variant = 0);
 
-// Copy blocks between the regions and a block-major host image: for i < n, r < n_regions,
+// Copy blocks between the regions and a block-major host image, to the image (to_host) or from it: for i < n, r < n_regions,
 //   host + ((i * row_regions + region0 + r) * block_bytes)  <->  bases[r] + ids[i]*block_bytes
-// `host` is the device address of pinned host memory, 16-byte aligned; n <= kMaxIdsPerLaunch, n_regions <= kMaxRegionsPerLaunch
-// (the caller splits larger requests; region0 / row_regions place a slice of the regions inside a row of the image).
-hipError_t launch_copy_blocks_to_host(void *const *bases, int n_regions, int region0, int row_regions, const int64_t *ids, int n,
-                                      size_t block_bytes, void *host, hipStream_t stream);
-hipError_t launch_copy_blocks_from_host(void *const *bases, int n_regions, int region0, int row_regions, const int64_t *ids,
-                                        int n, size_t block_bytes, const void *host, hipStream_t stream);
+// `host` is the device address of pinned host memory, 16-byte aligned, and is only read when !to_host; n <= kMaxIdsPerLaunch,
+// n_regions <= kMaxRegionsPerLaunch (the caller splits larger requests; region0 / row_regions place a slice of the regions
+// inside a row of the image).
+hipError_t launch_copy_blocks_host(bool to_host, void *const *bases, int n_regions, int region0, int row_regions,
+                                   const int64_t *ids, int n, size_t block_bytes, void *host, hipStream_t stream);
 
 // One lane: optionally store `value` to *p, then copy *p to *out_dev (the TLB self test's view of memory).
 hipError_t launch_peek_poke(void *p, unsigned *out_dev, unsigned value, bool do_write, hipStream_t stream);

@@ -28,7 +28,7 @@ BACKED = sorted(set(range(0, 3)) | set(range(1021, 1027)) | set(range(2046, 2051
                 | set(range(5117, 5120)))
 N_REGIONS = 4
 BLOCK_BYTES = [16, 1040, 2064, 18432, 32768, 49152, 497664, 2 * MiB]
-COMPACT_VARIANTS = [0, 1, 2, 3, 4, 5, 7, 8, 9, 10, 11]
+COMPACT_VARIANTS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11]
 
 
 def candidates(bb):
