@@ -272,6 +272,25 @@ int kvc_copy_blocks_to_host(int64_t group_id, const int64_t *block_ids, size_t n
 int kvc_copy_blocks_from_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, const void *host,
                               void *stream, int sync);
 
+/* encode_blocks_to_host / decode_blocks_from_host: the same two copies through a lossy codec that puts about half the bytes
+ * on the host link. The blocks hold 16-bit floats - the library does not know the element type of its tensors, so the codec
+ * number is the only statement of it and the caller answers for it. MXFP8: every 32 consecutive elements (64 bytes) become
+ * 32 OCP FP8 e4m3fn codes and one shared scale byte (E8M0, exponent + 127). The shared exponent is the smallest integer se
+ * with amax * 2^-se <= 448, clamped to [-127, 127] (-127 for an all-zero group), so nothing saturates; a code is
+ * v * 2^-se rounded to nearest even; decoding is code * 2^se rounded to the 16-bit type. A group that holds a NaN or an
+ * infinity gets the scale byte 0xFF and zero codes, and decodes to 32 quiet NaNs (0x7FC0 / 0x7E00). Relative error of a
+ * decoded element: at most 2^-4, or 2^(se-10) absolute for the small elements of a group.
+ * Host image: the record of (block i, region r) is at host + (i*R + r)*rec, rec = kvc_codec_record_bytes(codec, block_bytes)
+ * = block_bytes/2 + block_bytes/64: the block_bytes/2 codes in element order, then the block_bytes/64 scale bytes in group
+ * order; n*R*rec bytes in all. Refusals (KVC_E_INVALID, nothing launched) and KVC_E_NO_GPU as for kvc_copy_blocks_to_host /
+ * _from_host, and also: an unknown codec, block_bytes not a multiple of 1024. */
+enum { KVC_CODEC_MXFP8_BF16 = 1, KVC_CODEC_MXFP8_F16 = 2 };
+size_t kvc_codec_record_bytes(int codec, size_t block_bytes);   /* 0 for an unknown codec or unfit block_bytes */
+int kvc_encode_blocks_to_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, int codec,
+                              void *host, void *stream, int sync);
+int kvc_decode_blocks_from_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, int codec,
+                                const void *host, void *stream, int sync);
+
 /* Region bases of a group's KV tensors in map order (layer-major, K then V), for compact_blocks.
  * Returns the count; copies if cap suffices. */
 int64_t kvc_get_region_bases(int64_t group_id, void **out, int64_t cap);

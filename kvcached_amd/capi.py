@@ -131,6 +131,9 @@ SIGNATURES = {
     "kvc_get_region_bases": (_i64, [_i64, _VPP, _i64]),
     "kvc_copy_blocks_to_host": (_int, [_i64, _I64P, _sz, _sz, _vp, _vp, _int]),
     "kvc_copy_blocks_from_host": (_int, [_i64, _I64P, _sz, _sz, _vp, _vp, _int]),
+    "kvc_codec_record_bytes": (_sz, [_int, _sz]),
+    "kvc_encode_blocks_to_host": (_int, [_i64, _I64P, _sz, _sz, _int, _vp, _vp, _int]),
+    "kvc_decode_blocks_from_host": (_int, [_i64, _I64P, _sz, _sz, _int, _vp, _vp, _int]),
     "kvc_expand_block_ids": (_int, [_I64P, _sz, _i64, _vp, _vp]),
     "kvc_alloc_extend_indices": (_int, [_vp, _vp, _vp, _sz, _I64P, _sz, _i64, _vp, _sz, _vp]),
     "kvc_alloc_decode_indices": (_int, [_vp, _vp, _sz, _I64P, _sz, _i64, _vp, _vp]),
@@ -281,6 +284,28 @@ def copy_blocks_from_host(group_id: int, block_ids: Sequence[int], block_bytes: 
     """The block-major image at host_ptr (pinned memory) -> every region's copy of blocks `block_ids` (HIP kernel)."""
     check(lib.kvc_copy_blocks_from_host(group_id, i64_array(block_ids), len(block_ids), block_bytes, host_ptr or None,
                                         stream or None, int(sync)))
+
+
+KVC_CODEC_MXFP8_BF16, KVC_CODEC_MXFP8_F16 = 1, 2
+
+
+def codec_record_bytes(codec: int, block_bytes: int) -> int:
+    """Bytes of one (block, region) record of an encoded host image; 0 for an unknown codec or unfit block_bytes."""
+    return int(lib.kvc_codec_record_bytes(codec, block_bytes))
+
+
+def encode_blocks_to_host(group_id: int, block_ids: Sequence[int], block_bytes: int, codec: int, host_ptr: int,
+                          stream: int = 0, sync: bool = True) -> None:
+    """copy_blocks_to_host through a codec (KVC_CODEC_*): the image holds codec_record_bytes() per (block, region)."""
+    check(lib.kvc_encode_blocks_to_host(group_id, i64_array(block_ids), len(block_ids), block_bytes, codec,
+                                        host_ptr or None, stream or None, int(sync)))
+
+
+def decode_blocks_from_host(group_id: int, block_ids: Sequence[int], block_bytes: int, codec: int, host_ptr: int,
+                            stream: int = 0, sync: bool = True) -> None:
+    """copy_blocks_from_host from an image that encode_blocks_to_host wrote with the same codec."""
+    check(lib.kvc_decode_blocks_from_host(group_id, i64_array(block_ids), len(block_ids), block_bytes, codec,
+                                          host_ptr or None, stream or None, int(sync)))
 
 
 def get_region_bases(group_id: int = 0) -> List[int]:

@@ -470,15 +470,18 @@ int kvc_compact_blocks(void *const *region_bases, size_t n_regions, const int64_
 }
 
 namespace {
-// Host side of kvc_copy_blocks_{to,from}_host: arguments, the host buffer (pinned, 16-byte aligned, resolved to the address
-// the GPU reaches it at), then the allocator's own checks and the launch.
+// Host side of kvc_copy_blocks_{to,from}_host and, with a codec, of kvc_encode_blocks_to_host / kvc_decode_blocks_from_host:
+// arguments, the host buffer (pinned, 16-byte aligned, resolved to the address the GPU reaches it at), then the allocator's
+// own checks and the launch.
 int copy_blocks_host(bool to_host, int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, const void *host,
-                     void *stream, int sync) {
+                     void *stream, int sync, int codec = kCodecRaw) {
   return guarded([&]() -> int {
     GpuContext *ctx = KvAllocator::gpu();
     if (!ctx) throw NoGpuError("copying blocks to or from host memory needs init_kvcached on a GPU device");
     if (n && (!block_ids || !host)) throw InvalidError("NULL argument");
     if (block_bytes == 0 || block_bytes % 16 != 0) throw InvalidError("block_bytes must be a positive multiple of 16");
+    if (codec != kCodecRaw && codec != KVC_CODEC_MXFP8_BF16 && codec != KVC_CODEC_MXFP8_F16) throw InvalidError("unknown codec");
+    if (host_record_bytes(codec, block_bytes) == 0) throw InvalidError("block_bytes must be a multiple of 1024 for this codec");
     for (size_t i = 0; i < n; ++i)
       if (block_ids[i] < 0) throw InvalidError("negative block id");
     if (!to_host && n > 1) { // two copies into one block would race
@@ -498,7 +501,8 @@ int copy_blocks_host(bool to_host, int64_t group_id, const int64_t *block_ids, s
     char *dev = static_cast<char *>(attr.devicePointer);
     if (attr.hostPointer) dev += static_cast<const char *>(host) - static_cast<const char *>(attr.hostPointer);
     if (reinterpret_cast<uintptr_t>(dev) % 16 != 0) throw InvalidError("host buffer is not 16-byte aligned on the device side");
-    KvAllocator::global(group_id)->copy_blocks_host(to_host, block_ids, n, block_bytes, dev, static_cast<hipStream_t>(stream));
+    KvAllocator::global(group_id)->copy_blocks_host(to_host, block_ids, n, block_bytes, dev, static_cast<hipStream_t>(stream),
+                                                    codec);
     if (sync) ctx->sync(static_cast<hipStream_t>(stream));
     return KVC_OK;
   });
@@ -513,6 +517,23 @@ int kvc_copy_blocks_to_host(int64_t group_id, const int64_t *block_ids, size_t n
 int kvc_copy_blocks_from_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, const void *host,
                               void *stream, int sync) {
   return copy_blocks_host(false, group_id, block_ids, n, block_bytes, host, stream, sync);
+}
+
+static_assert(KVC_CODEC_MXFP8_BF16 == kCodecMxfp8Bf16 && KVC_CODEC_MXFP8_F16 == kCodecMxfp8F16, "the header's numbers are the kernels'");
+
+size_t kvc_codec_record_bytes(int codec, size_t block_bytes) {
+  return codec == kCodecRaw ? 0 : host_record_bytes(codec, block_bytes);
+}
+
+// (a codec number of 0 is not an encoding: these two refuse it instead of copying bytes)
+int kvc_encode_blocks_to_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, int codec, void *host,
+                              void *stream, int sync) {
+  return copy_blocks_host(true, group_id, block_ids, n, block_bytes, host, stream, sync, codec == kCodecRaw ? -1 : codec);
+}
+
+int kvc_decode_blocks_from_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, int codec,
+                                const void *host, void *stream, int sync) {
+  return copy_blocks_host(false, group_id, block_ids, n, block_bytes, host, stream, sync, codec == kCodecRaw ? -1 : codec);
 }
 
 int64_t kvc_get_region_bases(int64_t group_id, void **out, int64_t cap) {

@@ -580,14 +580,15 @@ void GpuContext::compact(void *const *bases, size_t n_regions, const int64_t *sr
 }
 
 void GpuContext::copy_blocks_host(bool to_host, void *const *bases, size_t n_regions, const int64_t *ids, size_t n,
-                                  size_t block_bytes, void *host, hipStream_t s) {
+                                  size_t block_bytes, void *host, hipStream_t s, int codec) {
   if (!s) s = stream_;
+  const size_t record = host_record_bytes(codec, block_bytes); // (the callers have refused a codec that gives 0)
   for (size_t r = 0; r < n_regions; r += kMaxRegionsPerLaunch) {
     const int nr = (int)std::min<size_t>(kMaxRegionsPerLaunch, n_regions - r);
     for (size_t i = 0; i < n; i += kMaxIdsPerLaunch) {
       const int ni = (int)std::min<size_t>(kMaxIdsPerLaunch, n - i);
-      char *h = static_cast<char *>(host) + i * n_regions * block_bytes; // row i of the image
-      HIP_CHECK(launch_copy_blocks_host(to_host, bases + r, nr, (int)r, (int)n_regions, ids + i, ni, block_bytes, h, s));
+      char *h = static_cast<char *>(host) + i * n_regions * record; // row i of the image
+      HIP_CHECK(launch_copy_blocks_host(to_host, bases + r, nr, (int)r, (int)n_regions, ids + i, ni, block_bytes, h, s, codec));
     }
   }
 }

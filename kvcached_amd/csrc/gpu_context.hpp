@@ -112,9 +112,10 @@ public:
   void zero_fill(void *const *pages, size_t n, size_t page_bytes, hipStream_t s);
   void compact(void *const *bases, size_t n_regions, const int64_t *src, const int64_t *dst, size_t n_moves,
                size_t block_bytes, hipStream_t s);
-  // blocks <-> a block-major host image (copy_blocks_to_host / _from_host); `host` is a device address of pinned memory
+  // blocks <-> a block-major host image (copy_blocks_to_host / _from_host, or encode_ / decode_ with a codec: HostCodec of
+  // kernels.hpp); `host` is a device address of pinned memory
   void copy_blocks_host(bool to_host, void *const *bases, size_t n_regions, const int64_t *ids, size_t n, size_t block_bytes,
-                        void *host, hipStream_t s);
+                        void *host, hipStream_t s, int codec = 0);
   void sync(hipStream_t s); // hipStreamSynchronize + harvest event timings
   // ---- zeroing pages on their way BACK (drm backend, extents with an alias mapping).
   // A page handed out by map_slots must read zero. Filling it there puts 0.3 us per page of GPU time between the

@@ -1,7 +1,8 @@
-// kernels.hip — the two device kernels of the path, written for gfx950 (CDNA4) only.
+// kernels.hip — the device kernels of the path, written for gfx950 (CDNA4) only.
 //
-// Both are pure byte movers and HBM-bound (no MFMA: there is no contraction anywhere on this
-// path). What matters on MI355X, and what the code below does:
+// All are byte movers, bound by HBM or by the host link (no MFMA: there is no contraction anywhere on this path); the only
+// arithmetic is the opt-in MXFP8 codec of the host copies (encode_blocks_to_host / decode_blocks_from_host, at the end).
+// What matters on MI355X, and what the code below does:
 //   * every wave-instruction touches 64 lanes x 16 B = 1 KiB of contiguous memory
 //     (global_store_dwordx4 / global_load_dwordx4 / global_load_lds_dwordx4);
 //   * one workgroup per 64 KiB slab (fill) or per <=32 KiB tile (compaction) and NO grid-stride
@@ -369,14 +370,27 @@ struct HostCopyArgs {
 };
 static_assert(sizeof(HostCopyArgs) <= 12 * 1024, "kernarg segment budget");
 
+// Which (block, region) pair and which tile of it this workgroup has: the device address of the tile, the index of the pair's
+// record in the host image, and the tile number. Tile-fastest, then region, then block.
+struct HostTile {
+  char *dev;
+  size_t record;
+  unsigned t;
+};
+__device__ __forceinline__ HostTile host_tile(const HostCopyArgs &a, unsigned n_regions, unsigned region0, unsigned row_regions,
+                                              unsigned tiles, unsigned block_bytes) {
+  const unsigned pair = blockIdx.x / tiles, t = blockIdx.x - pair * tiles;
+  const unsigned i = pair / n_regions, r = pair - i * n_regions;
+  return {tile_address<kTile16>(a.base[r], a.id[i], block_bytes, t), (size_t)i * row_regions + region0 + r, t};
+}
+
 template <bool TO_HOST>
 __device__ __forceinline__ void copy_blocks_host_tile(const HostCopyArgs &a, char *host, unsigned n_regions, unsigned region0,
                                                       unsigned row_regions, unsigned tiles, unsigned block_bytes) {
-  const unsigned pair = blockIdx.x / tiles, t = blockIdx.x - pair * tiles;
-  const unsigned i = pair / n_regions, r = pair - i * n_regions;
-  char *dev = tile_address<kTile16>(a.base[r], a.id[i], block_bytes, t);
-  char *hst = host + ((size_t)i * row_regions + region0 + r) * block_bytes + (size_t)t * kTile16;
-  copy_tile<kTile16, false, TO_HOST, !TO_HOST, true, true>(TO_HOST ? dev : hst, TO_HOST ? hst : dev, block_bytes - t * kTile16);
+  const HostTile w = host_tile(a, n_regions, region0, row_regions, tiles, block_bytes);
+  char *hst = host + w.record * block_bytes + (size_t)w.t * kTile16;
+  copy_tile<kTile16, false, TO_HOST, !TO_HOST, true, true>(TO_HOST ? w.dev : hst, TO_HOST ? hst : w.dev,
+                                                           block_bytes - w.t * kTile16);
 }
 
 // (two named kernels rather than one template: a profile names the direction)
@@ -392,11 +406,177 @@ __global__ __launch_bounds__(kCopyThreads) void copy_blocks_from_host_kernel(Hos
   copy_blocks_host_tile<false>(a, host, n_regions, region0, row_regions, tiles, block_bytes);
 }
 
+// ---------------------------------------------------------------------------- encode_blocks_to_host / decode_blocks_from_host
+// The same copies through the MXFP8 codec (KVCacheManager.offload(codec="mxfp8"); the format: INTEGRATION.md §6): the blocks
+// hold bf16 or fp16, and a group of 32 consecutive elements (64 bytes) crosses the link as 32 e4m3fn codes and one shared
+// power-of-two scale byte (E8M0) - 33 bytes for 64. The record of a (block, region) pair is its block_bytes / 2 codes in
+// element order, then its block_bytes / 64 scale bytes in group order, at host + record index * (block_bytes / 2 +
+// block_bytes / 64). block_bytes is a multiple of 1 KiB, so a tile is whole pieces and every predicate below is wave-uniform.
+// Work decomposition, placement of the waves' pieces and the memory accesses are those of copy_blocks_host_tile: a lane's
+// 16-byte access on the HBM side is 8 elements, a group is one quad of lanes (a DPP quad_perm reduction, no LDS, no
+// barrier), a lane's codes of a piece are one 8-byte access on the host side, and the 16 scale bytes of a piece are ONE
+// 16-byte access by one lane: lane k of a wave has those of the wave's piece k, gathered / spread with v_readlane.
+// The arithmetic is integer work on the bit patterns plus fp32 multiplications by powers of two (exact): it does not use
+// the scaled-conversion instructions of gfx950, whose rounding and scale handling nothing here could check to the bit.
+// fp32 denormals (bf16 groups below 2^-100, outside what the tests pin) follow the kernel's float mode.
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+static constexpr int kCodecPieces = kTile16 / kPiece / kCopyWaves; // per wave
+
+__device__ __forceinline__ unsigned quad_max(unsigned x) { // the maximum over the lane's quad, in every lane of it
+  const unsigned y = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, true)); // quad_perm:[1,0,3,2]
+  return max(y, (unsigned)__builtin_amdgcn_mov_dpp((int)y, 0x4E, 0xF, 0xF, true));             // quad_perm:[2,3,0,1]
+}
+
+// The 16-bit float types by their bit patterns. kInf: the magnitude pattern of infinity (everything above is a NaN).
+template <bool F16>
+struct Half16 {
+  static constexpr unsigned kInf = F16 ? 0x7c00u : 0x7f80u, kQuietNan = F16 ? 0x7e00u : 0x7fc0u;
+  static __device__ __forceinline__ float to_float(unsigned h) {
+    if (F16) return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
+    return __uint_as_float(h << 16);
+  }
+  static __device__ __forceinline__ unsigned from_float(float f) { // round to nearest even; subnormals of fp16 are kept
+    if (F16) return __builtin_bit_cast(unsigned short, (_Float16)f);
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x7fffffffu) > 0x7f800000u ? kQuietNan : (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
+  }
+  // Scale byte (shared exponent + 127) of a group whose largest magnitude has the finite pattern `amax`: with amax = m * 2^e,
+  // m in [1, 2), the exponent is e - 8 for m <= 1.75 and e - 7 above, clamped to >= -127 (bf16; fp16 never gets there).
+  static __device__ __forceinline__ unsigned scale_byte(unsigned amax) {
+    if (F16) {
+      if (amax == 0) return 0;
+      unsigned e = amax >> 10, m = amax & 0x3ffu;
+      if (e == 0) { // subnormal: amax = m * 2^-24; normalise
+        const unsigned p = 31u - (unsigned)__builtin_clz(m);
+        m = (m << (10u - p)) & 0x3ffu;
+        return p + 95u + (m > 0x300u);
+      }
+      return e + 104u + (m > 0x300u);
+    }
+    const int b = (int)(amax >> 7) - 8 + ((amax & 0x7fu) > 0x60u); // (zero and the subnormals, exponent field 0, clamp to 0)
+    return (unsigned)max(b, 0);
+  }
+};
+
+// The signs travel as bits, beside the floating-point operations: the compiler fuses a multiplication with the conversion
+// next to it (v_fma_mix*, a * b + 0), and -0 + 0 is +0.
+// |x|, 0 <= |x| <= 448, to the seven low bits of its e4m3fn code, round to nearest even.
+__device__ __forceinline__ unsigned e4m3_magnitude_code(float x) {
+  const unsigned a = __float_as_uint(x) & 0x7fffffffu;
+  if (a >= 0x3c800000u) // >= 2^-6, a normal number of e4m3: round the 23-bit mantissa to 3 bits, rebias 127 -> 7
+    return min(((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - 0x3c0u, 0x7eu);
+  // a multiple of 2^-9: 2^14 + |x| has 2^-9 as its last mantissa bit, and the addition rounds to nearest even
+  return __float_as_uint(__uint_as_float(a) + 16384.0f) - 0x46800000u;
+}
+
+// The magnitude of the e4m3fn code c (its sign bit is ignored).
+__device__ __forceinline__ float e4m3_magnitude(unsigned c) {
+  const unsigned em = c & 0x7fu;
+  return em == 0x7fu ? __uint_as_float(0x7fc00000u)
+         : em >= 8u  ? __uint_as_float((em << 20) + 0x3c000000u)
+                     : (float)em * 0.001953125f; // subnormal: em * 2^-9
+}
+
+template <bool F16, bool TO_HOST>
+__device__ __forceinline__ void codec_blocks_host_tile(const HostCopyArgs &a, char *host, unsigned n_regions, unsigned region0,
+                                                       unsigned row_regions, unsigned tiles, unsigned block_bytes) {
+  using H = Half16<F16>;
+  const HostTile w = host_tile(a, n_regions, region0, row_regions, tiles, block_bytes);
+  char *record = host + w.record * (size_t)(block_bytes / 2 + block_bytes / 64);
+  char *codes = record + (size_t)w.t * (kTile16 / 2);
+  char *scales = record + block_bytes / 2 + (size_t)w.t * (kTile16 / 64);
+  const unsigned pieces = min(block_bytes - w.t * kTile16, (unsigned)kTile16) / kPiece; // of this tile
+  // (readfirstlane: tells the compiler that the wave number, and so every test of a piece against `pieces`, is wave-uniform)
+  const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  auto piece = [&](unsigned k) -> unsigned { return k * kCopyWaves + wave; }; // as copy_tile's INTERLEAVED
+  const bool scale_lane = lane < (unsigned)kCodecPieces && piece(lane) < pieces; // lane k: the 16 scale bytes of piece k
+  if (TO_HOST) {
+    v4u v[kCodecPieces];
+#pragma unroll
+    for (int k = 0; k < kCodecPieces; ++k)
+      if (piece(k) < pieces) v[k] = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(w.dev + piece(k) * kPiece) + lane);
+    unsigned quad_scales = 0; // byte k: the scale byte of this lane's group in piece k
+#pragma unroll
+    for (int k = 0; k < kCodecPieces; ++k) {
+      if (piece(k) >= pieces) continue;
+      unsigned amax = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) amax = max(amax, max(v[k][j] & 0x7fffu, (v[k][j] >> 16) & 0x7fffu));
+      amax = quad_max(amax);
+      const bool finite = amax < H::kInf;
+      const unsigned sb = finite ? H::scale_byte(amax) : 0xffu;
+      const float down = __uint_as_float((254u - sb) << 23); // 2^-(sb - 127); sb <= 247 for a finite group
+      v2u c = {0u, 0u};
+      if (finite) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const unsigned lo = e4m3_magnitude_code(H::to_float(v[k][j] & 0x7fffu) * down),
+                         hi = e4m3_magnitude_code(H::to_float((v[k][j] >> 16) & 0x7fffu) * down);
+          const unsigned signs = ((v[k][j] >> 8) & 0x80u) | ((v[k][j] >> 16) & 0x8000u);
+          c[j >> 1] |= (lo | (hi << 8) | signs) << ((j & 1) * 16);
+        }
+      }
+      quad_scales |= sb << (k * 8);
+      *(reinterpret_cast<v2u *>(codes + piece(k) * (kPiece / 2)) + lane) = c;
+    }
+    v4u s;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s[j] = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) // group 4j + b of every piece, from the first lane of its quad; this lane keeps its piece's
+        s[j] |= ((__builtin_amdgcn_readlane((int)quad_scales, (4 * j + b) * 4) >> ((lane & 3u) * 8)) & 0xffu) << (b * 8);
+    }
+    if (scale_lane) *reinterpret_cast<v4u *>(scales + piece(lane) * (kPiece / 64)) = s;
+  } else {
+    v2u c[kCodecPieces];
+    v4u s = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < kCodecPieces; ++k)
+      if (piece(k) < pieces) c[k] = *(reinterpret_cast<const v2u *>(codes + piece(k) * (kPiece / 2)) + lane);
+    if (scale_lane) s = *reinterpret_cast<const v4u *>(scales + piece(lane) * (kPiece / 64));
+#pragma unroll
+    for (int k = 0; k < kCodecPieces; ++k) {
+      if (piece(k) >= pieces) continue;
+      unsigned word = 0; // the four scale bytes that hold this lane's group (lane / 4) of piece k
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned sj = (unsigned)__builtin_amdgcn_readlane((int)s[j], k);
+        word = (lane >> 4) == (unsigned)j ? sj : word;
+      }
+      const unsigned sb = (word >> (((lane >> 2) & 3u) * 8)) & 0xffu;
+      const float up = __uint_as_float(sb ? sb << 23 : 0x00400000u); // 2^(sb - 127)
+      v4u out;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned pair = (c[k][j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+        const unsigned lo = H::from_float(e4m3_magnitude(pair) * up), hi = H::from_float(e4m3_magnitude(pair >> 8) * up);
+        const unsigned signs = ((pair & 0x80u) << 8) | ((pair & 0x8000u) << 16);
+        out[j] = sb == 0xffu ? H::kQuietNan * 0x10001u : lo | (hi << 16) | signs;
+      }
+      __builtin_nontemporal_store(out, reinterpret_cast<v4u *>(w.dev + piece(k) * kPiece) + lane);
+    }
+  }
+}
+
+// (named kernels, as above: a profile names the direction and the element type)
+#define KVC_CODEC_KERNEL(name, F16, TO_HOST)                                                                                  \
+  __global__ __launch_bounds__(kCopyThreads) void name(HostCopyArgs a, char *host, unsigned n_regions, unsigned region0,       \
+                                                       unsigned row_regions, unsigned tiles, unsigned block_bytes) {           \
+    codec_blocks_host_tile<F16, TO_HOST>(a, host, n_regions, region0, row_regions, tiles, block_bytes);                        \
+  }
+KVC_CODEC_KERNEL(encode_blocks_to_host_bf16_kernel, false, true)
+KVC_CODEC_KERNEL(encode_blocks_to_host_f16_kernel, true, true)
+KVC_CODEC_KERNEL(decode_blocks_from_host_bf16_kernel, false, false)
+KVC_CODEC_KERNEL(decode_blocks_from_host_f16_kernel, true, false)
+#undef KVC_CODEC_KERNEL
+
 hipError_t launch_copy_blocks_host(bool to_host, void *const *bases, int n_regions, int region0, int row_regions,
-                                   const int64_t *ids, int n, size_t block_bytes, void *host, hipStream_t stream) {
+                                   const int64_t *ids, int n, size_t block_bytes, void *host, hipStream_t stream, int codec) {
   if (n_regions <= 0 || n <= 0) return hipSuccess;
   if (n_regions > kMaxRegionsPerLaunch || n > kMaxIdsPerLaunch || region0 < 0 || row_regions < region0 + n_regions ||
-      block_bytes == 0 || block_bytes % 16 != 0 || block_bytes > 0x7fffffffull || reinterpret_cast<uintptr_t>(host) % 16 != 0)
+      block_bytes == 0 || block_bytes % 16 != 0 || block_bytes > 0x7fffffffull || reinterpret_cast<uintptr_t>(host) % 16 != 0 ||
+      host_record_bytes(codec, block_bytes) == 0)
     return hipErrorInvalidValue;
   HostCopyArgs a;
   if (!copy_bases(a.base, bases, n_regions)) return hipErrorInvalidValue;
@@ -407,10 +587,13 @@ hipError_t launch_copy_blocks_host(bool to_host, void *const *bases, int n_regio
   const unsigned tiles = (unsigned)((block_bytes + kTile16 - 1) / kTile16);
   const size_t grid = (size_t)tiles * (size_t)n * (size_t)n_regions;
   if (grid > 0x7fffffffull) return hipErrorInvalidValue;
-  const auto kernel = to_host ? copy_blocks_to_host_kernel : copy_blocks_from_host_kernel;
-  kernel<<<dim3((unsigned)grid), dim3(kCopyThreads), 0, stream>>>(a, static_cast<char *>(host), (unsigned)n_regions,
-                                                                  (unsigned)region0, (unsigned)row_regions, tiles,
-                                                                  (unsigned)block_bytes);
+  // row: the codec of the host image (kCodecRaw, kCodecMxfp8Bf16, kCodecMxfp8F16); column: from the host, to the host
+  using HostKernel = void (*)(HostCopyArgs, char *, unsigned, unsigned, unsigned, unsigned, unsigned);
+  static const HostKernel kernels[3][2] = {{copy_blocks_from_host_kernel, copy_blocks_to_host_kernel},
+                                           {decode_blocks_from_host_bf16_kernel, encode_blocks_to_host_bf16_kernel},
+                                           {decode_blocks_from_host_f16_kernel, encode_blocks_to_host_f16_kernel}};
+  kernels[codec][to_host ? 1 : 0]<<<dim3((unsigned)grid), dim3(kCopyThreads), 0, stream>>>(
+      a, static_cast<char *>(host), (unsigned)n_regions, (unsigned)region0, (unsigned)row_regions, tiles, (unsigned)block_bytes);
   return hipGetLastError();
 }
 

@@ -28,13 +28,26 @@ hipError_t launch_zero_fill_pages(void *const *pages, int n, size_t page_bytes, 
 hipError_t launch_compact_blocks(void *const *bases, int n_regions, const int64_t *src, const int64_t *dst, int n_moves,
                                  size_t block_bytes, hipStream_t stream, int variant = 0);
 
+// What a (block, region) pair of the host image holds (the KVC_CODEC_* numbers of the C ABI; 0 = the bytes themselves).
+enum HostCodec { kCodecRaw = 0, kCodecMxfp8Bf16 = 1, kCodecMxfp8F16 = 2 };
+// Bytes of one (block, region) record of the host image; 0 for an unknown codec or a block size the codec cannot take.
+// MXFP8: one e4m3fn code per 16-bit element and one scale byte per 32 elements; whole 1 KiB pieces only (one wave-instruction
+// of the tile copy), which also keeps every record and every 512 B + 16 B part of it 16-byte aligned.
+inline size_t host_record_bytes(int codec, size_t block_bytes) {
+  if (codec == kCodecRaw) return block_bytes;
+  if ((codec != kCodecMxfp8Bf16 && codec != kCodecMxfp8F16) || block_bytes == 0 || block_bytes % 1024 != 0) return 0;
+  return block_bytes / 2 + block_bytes / 64;
+}
+
 // Copy blocks between the regions and a block-major host image, to the image (to_host) or from it: for i < n, r < n_regions,
-//   host + ((i * row_regions + region0 + r) * block_bytes)  <->  bases[r] + ids[i]*block_bytes
+//   host + ((i * row_regions + region0 + r) * record)  <->  bases[r] + ids[i]*block_bytes
+// with record = host_record_bytes(codec, block_bytes): the block's bytes, or their MXFP8 encoding (kernels.hip has the layout).
 // `host` is the device address of pinned host memory, 16-byte aligned, and is only read when !to_host; n <= kMaxIdsPerLaunch,
 // n_regions <= kMaxRegionsPerLaunch (the caller splits larger requests; region0 / row_regions place a slice of the regions
 // inside a row of the image).
 hipError_t launch_copy_blocks_host(bool to_host, void *const *bases, int n_regions, int region0, int row_regions,
-                                   const int64_t *ids, int n, size_t block_bytes, void *host, hipStream_t stream);
+                                   const int64_t *ids, int n, size_t block_bytes, void *host, hipStream_t stream,
+                                   int codec = kCodecRaw);
 
 // One lane: optionally store `value` to *p, then copy *p to *out_dev (the TLB self test's view of memory).
 hipError_t launch_peek_poke(void *p, unsigned *out_dev, unsigned value, bool do_write, hipStream_t stream);

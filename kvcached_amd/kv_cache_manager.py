@@ -528,13 +528,19 @@ class KVCacheManager:
                     raise ValueError(f"block {b} is free")
 
     @synchronized
-    def offload(self, block_ids: List[int], out: Optional["torch.Tensor"] = None) -> "OffloadedBlocks":
+    def offload(self, block_ids: List[int], out: Optional["torch.Tensor"] = None, codec: Optional[str] = None,
+                dtype: Optional["torch.dtype"] = None) -> "OffloadedBlocks":
         """Copy live blocks to pinned host memory, wait until the bytes are there, and free the blocks.
 
         The copy runs on torch.cuda.current_stream(), behind whatever the engine queued there. `out` (optional): a
-        pinned, contiguous uint8 tensor with room for len(block_ids) * n_regions * block_bytes bytes. Raises ValueError
-        (nothing changed) for an empty or duplicated id list, the null block, a free or a reserved block, or an unfit
-        `out`; RuntimeError when the KV tensors live in other processes (tensor parallelism, worker IPC)."""
+        pinned, contiguous uint8 tensor with room for len(block_ids) * n_regions * block_bytes bytes. `codec` (optional,
+        lossy): "mxfp8" stores the blocks as OCP FP8 codes with one shared power-of-two scale per 32 elements
+         - 33/64 of the bytes on the link and in `out`, which then needs len(block_ids) * n_regions *
+        (block_bytes / 2 + block_bytes / 64) bytes; `dtype` (torch.bfloat16 or torch.float16) then names the element type
+        of the KV tensors, which the manager itself does not know. Raises ValueError (nothing changed) for an empty or
+        duplicated id list, the null block, a free or a reserved block, an unfit `out`, an unknown codec, a missing or
+        unfit dtype, or block bytes the codec cannot take (not a multiple of 1024); RuntimeError when the KV tensors
+        live in other processes (tensor parallelism, worker IPC)."""
         self._wait_post_init()
         if self._kv_remote:
             raise RuntimeError("offload needs the KV tensors in this process (world_size == 1, no worker IPC); "
@@ -544,7 +550,11 @@ class KVCacheManager:
         import torch
         from kvcached_amd import capi
         bases, block_bytes = self._block_geometry()
-        nbytes = len(ids) * len(bases) * block_bytes
+        codec_id = _codec_number(codec, dtype)
+        record = capi.codec_record_bytes(codec_id, block_bytes) if codec_id else block_bytes
+        if not record:
+            raise ValueError(f"codec {codec!r} needs blocks of a multiple of 1024 bytes, not {block_bytes}")
+        nbytes = len(ids) * len(bases) * record
         if out is None:
             # pinned wherever a GPU exists; without one the library refuses the copy anyway (KVC_E_NO_GPU)
             out = torch.empty(nbytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
@@ -552,15 +562,21 @@ class KVCacheManager:
               or not out.is_pinned()):
             raise ValueError(f"out must be a pinned, contiguous uint8 CPU tensor of at least {nbytes} bytes")
         data = out.view(-1)[:nbytes]
-        _on_current_stream(lambda s: capi.copy_blocks_to_host(self.group_id, ids, block_bytes, data.data_ptr(), s, sync=True))
+        if codec_id:
+            _on_current_stream(lambda s: capi.encode_blocks_to_host(self.group_id, ids, block_bytes, codec_id,
+                                                                    data.data_ptr(), s, sync=True))
+        else:
+            _on_current_stream(lambda s: capi.copy_blocks_to_host(self.group_id, ids, block_bytes, data.data_ptr(), s, sync=True))
         self.free(ids)   # only now: free() may unmap pages, and the copy has read them
-        return OffloadedBlocks(ids, data, self._geometry_key(len(bases), block_bytes))
+        return OffloadedBlocks(ids, data, self._geometry_key(len(bases), block_bytes), codec=codec if codec_id else None,
+                               dtype=dtype if codec_id else None)
 
     @synchronized
     def restore(self, handle: "OffloadedBlocks") -> Optional[List[int]]:
         """Allocate len(handle.block_ids) blocks and copy the offloaded bytes into them: new_ids[i] holds
-        handle.block_ids[i]. Returns None (nothing changed) when the pool cannot hold them. The copy is queued on
-        torch.cuda.current_stream() and not waited for: later work on that stream sees the data."""
+        handle.block_ids[i] - through the decoder of the handle's codec, if it has one. Returns None (nothing changed)
+        when the pool cannot hold them. The copy is queued on torch.cuda.current_stream() and not waited for: later work
+        on that stream sees the data."""
         self._wait_post_init()
         if self._kv_remote:
             raise RuntimeError("restore needs the KV tensors in this process (world_size == 1, no worker IPC)")
@@ -572,17 +588,39 @@ class KVCacheManager:
         if handle.geometry != key:
             raise ValueError(f"offloaded blocks of geometry {handle.geometry} (group, contiguous, regions, block bytes) "
                              f"cannot be restored into {key}")
+        codec_id = _codec_number(handle.codec, handle.dtype)
         new_ids = self.alloc(len(handle.block_ids))
         if new_ids is None:
             return None
         try:
-            _on_current_stream(lambda s: capi.copy_blocks_from_host(self.group_id, new_ids, block_bytes,
-                                                                    handle.data.data_ptr(), s, sync=False))
+            if codec_id:
+                _on_current_stream(lambda s: capi.decode_blocks_from_host(self.group_id, new_ids, block_bytes, codec_id,
+                                                                          handle.data.data_ptr(), s, sync=False))
+            else:
+                _on_current_stream(lambda s: capi.copy_blocks_from_host(self.group_id, new_ids, block_bytes,
+                                                                        handle.data.data_ptr(), s, sync=False))
         except Exception:
             self.free(new_ids)
             raise
         handle._record()
         return new_ids
+
+
+def _codec_number(codec: Optional[str], dtype: Any) -> int:
+    """The C ABI's KVC_CODEC_* number of (codec, element type); 0 for no codec. ValueError for what does not exist."""
+    if codec is None:
+        if dtype is not None:
+            raise ValueError("dtype is only meaningful with a codec")
+        return 0
+    if codec != "mxfp8":
+        raise ValueError(f"unknown codec {codec!r} (known: 'mxfp8')")
+    import torch
+    from kvcached_amd import capi
+    numbers = {torch.bfloat16: capi.KVC_CODEC_MXFP8_BF16, torch.float16: capi.KVC_CODEC_MXFP8_F16}
+    if dtype not in numbers:
+        raise ValueError(f"codec 'mxfp8' needs dtype=torch.bfloat16 or torch.float16 (the element type of the KV tensors), "
+                         f"not {dtype!r}")
+    return numbers[dtype]
 
 
 _side_streams: Dict[int, Any] = {}
@@ -613,14 +651,18 @@ class OffloadedBlocks:
     """What KVCacheManager.offload() returns: the bytes of offloaded blocks in pinned host memory.
 
     block_ids: the ids the blocks had (restore()'s result is in the same order); data: the pinned uint8 image,
-    block-major ([block][region][block_bytes]); geometry: (group_id, contiguous layout, regions, block_bytes);
+    block-major ([block][region][block_bytes], or [block][region][codes, scale bytes] under a codec); geometry:
+    (group_id, contiguous layout, regions, block_bytes); codec, dtype: what offload() was given (None, None: raw bytes);
     event: the event behind the latest restore() copy (None before the first). The pinned buffer is not given back -
     by release() or by garbage collection - before every restore() copy from it has finished."""
 
-    def __init__(self, block_ids: List[int], data: "torch.Tensor", geometry: Tuple[int, bool, int, int]):
+    def __init__(self, block_ids: List[int], data: "torch.Tensor", geometry: Tuple[int, bool, int, int],
+                 codec: Optional[str] = None, dtype: Any = None):
         self.block_ids = list(block_ids)
         self.data = data
         self.geometry = geometry
+        self.codec = codec
+        self.dtype = dtype
         self._events: List[Any] = []
 
     @property
