@@ -30,7 +30,7 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = "gfx950"
 
 LIB_SRCS = ["c_api.cpp", "kv_allocator.cpp", "gpu_context.cpp", "page_allocator.cpp", "kernels.hip", "index_kernels.hip"]
-LIB_DEPS = LIB_SRCS + ["common.hpp", "hip_vmm.hpp", "drm_vm.hpp", "extent_pool.hpp", "gpu_context.hpp", "kernels.hpp", "kv_allocator.hpp", "mem_info.hpp",
+LIB_DEPS = LIB_SRCS + ["codec_math.hpp", "common.hpp", "hip_vmm.hpp", "drm_vm.hpp", "extent_pool.hpp", "gpu_context.hpp", "kernels.hpp", "kv_allocator.hpp", "mem_info.hpp",
                        "page_allocator.hpp", "run_scan.hpp", "../../include/kvcached_amd.h"]
 EXT_SRCS = ["vmm_ops.cpp"]
 

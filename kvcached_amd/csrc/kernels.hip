@@ -17,6 +17,7 @@
 // for a 2 MiB page) and reads nothing; compact_blocks reads + writes block_bytes per
 // (region, move) = 2 x block_bytes x n_regions per moved block.
 
+#include "codec_math.hpp"
 #include "kernels.hpp"
 
 namespace kvc {
@@ -418,7 +419,7 @@ __global__ __launch_bounds__(kCopyThreads) void copy_blocks_from_host_kernel(Hos
 // 16-byte access by one lane: lane k of a wave has those of the wave's piece k, gathered / spread with v_readlane.
 // The arithmetic is integer work on the bit patterns plus fp32 multiplications by powers of two (exact): it does not use
 // the scaled-conversion instructions of gfx950, whose rounding and scale handling nothing here could check to the bit.
-// fp32 denormals (bf16 groups below 2^-100, outside what the tests pin) follow the kernel's float mode.
+// fp32 denormals (bf16 groups below 2^-100) are kept - the float mode hipcc gives these kernels - and the tests pin them too.
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 static constexpr int kCodecPieces = kTile16 / kPiece / kCopyWaves; // per wave
 
@@ -427,55 +428,8 @@ __device__ __forceinline__ unsigned quad_max(unsigned x) { // the maximum over t
   return max(y, (unsigned)__builtin_amdgcn_mov_dpp((int)y, 0x4E, 0xF, 0xF, true));             // quad_perm:[2,3,0,1]
 }
 
-// The 16-bit float types by their bit patterns. kInf: the magnitude pattern of infinity (everything above is a NaN).
-template <bool F16>
-struct Half16 {
-  static constexpr unsigned kInf = F16 ? 0x7c00u : 0x7f80u, kQuietNan = F16 ? 0x7e00u : 0x7fc0u;
-  static __device__ __forceinline__ float to_float(unsigned h) {
-    if (F16) return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
-    return __uint_as_float(h << 16);
-  }
-  static __device__ __forceinline__ unsigned from_float(float f) { // round to nearest even; subnormals of fp16 are kept
-    if (F16) return __builtin_bit_cast(unsigned short, (_Float16)f);
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x7fffffffu) > 0x7f800000u ? kQuietNan : (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
-  }
-  // Scale byte (shared exponent + 127) of a group whose largest magnitude has the finite pattern `amax`: with amax = m * 2^e,
-  // m in [1, 2), the exponent is e - 8 for m <= 1.75 and e - 7 above, clamped to >= -127 (bf16; fp16 never gets there).
-  static __device__ __forceinline__ unsigned scale_byte(unsigned amax) {
-    if (F16) {
-      if (amax == 0) return 0;
-      unsigned e = amax >> 10, m = amax & 0x3ffu;
-      if (e == 0) { // subnormal: amax = m * 2^-24; normalise
-        const unsigned p = 31u - (unsigned)__builtin_clz(m);
-        m = (m << (10u - p)) & 0x3ffu;
-        return p + 95u + (m > 0x300u);
-      }
-      return e + 104u + (m > 0x300u);
-    }
-    const int b = (int)(amax >> 7) - 8 + ((amax & 0x7fu) > 0x60u); // (zero and the subnormals, exponent field 0, clamp to 0)
-    return (unsigned)max(b, 0);
-  }
-};
-
-// The signs travel as bits, beside the floating-point operations: the compiler fuses a multiplication with the conversion
-// next to it (v_fma_mix*, a * b + 0), and -0 + 0 is +0.
-// |x|, 0 <= |x| <= 448, to the seven low bits of its e4m3fn code, round to nearest even.
-__device__ __forceinline__ unsigned e4m3_magnitude_code(float x) {
-  const unsigned a = __float_as_uint(x) & 0x7fffffffu;
-  if (a >= 0x3c800000u) // >= 2^-6, a normal number of e4m3: round the 23-bit mantissa to 3 bits, rebias 127 -> 7
-    return min(((a + 0x7ffffu + ((a >> 20) & 1u)) >> 20) - 0x3c0u, 0x7eu);
-  // a multiple of 2^-9: 2^14 + |x| has 2^-9 as its last mantissa bit, and the addition rounds to nearest even
-  return __float_as_uint(__uint_as_float(a) + 16384.0f) - 0x46800000u;
-}
-
-// The magnitude of the e4m3fn code c (its sign bit is ignored).
-__device__ __forceinline__ float e4m3_magnitude(unsigned c) {
-  const unsigned em = c & 0x7fu;
-  return em == 0x7fu ? __uint_as_float(0x7fc00000u)
-         : em >= 8u  ? __uint_as_float((em << 20) + 0x3c000000u)
-                     : (float)em * 0.001953125f; // subnormal: em * 2^-9
-}
+// Half16<F16>, e4m3_magnitude_code and e4m3_magnitude - the steps without lane intrinsics - are in codec_math.hpp, which also
+// compiles as plain C++ so that the tests can enumerate them on the CPU.
 
 template <bool F16, bool TO_HOST>
 __device__ __forceinline__ void codec_blocks_host_tile(const HostCopyArgs &a, char *host, unsigned n_regions, unsigned region0,

@@ -5,7 +5,9 @@ compares the encode / decode kernels against, bit for bit.
 A group is 32 consecutive 16-bit floats. Its shared exponent se is the smallest integer with amax * 2^-se <= 448 (the
 largest e4m3fn value), clamped to [-127, 127], -127 for an all-zero group; the scale byte is se + 127 (E8M0); the code of
 an element v is v * 2^-se rounded to e4m3fn, to nearest even. A group that holds a NaN or an infinity has the scale byte
-0xFF and 32 zero codes, and decodes to 32 canonical quiet NaNs."""
+0xFF and 32 zero codes, and decodes to 32 canonical quiet NaNs. A NaN code (0x7F or 0xFF) under a scale byte other than
+0xFF is never written by the encoder and decodes to a NaN of unspecified sign and payload. (tests/kvc_mx_exact.py states
+the same format in exact float64 arithmetic; tests/test_kv_codec.py holds the two against each other on every input.)"""
 import torch
 
 GROUP = 32

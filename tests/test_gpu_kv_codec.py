@@ -1,9 +1,16 @@
 """The MXFP8 codec of KV block offload on a real MI355X: encode_blocks_to_host / decode_blocks_from_host against the CPU
 restatement of the format (tests/kvc_mx_ref.py), bit for bit, and KVCacheManager.offload(codec="mxfp8") / .restore.
 
-What "bit for bit" covers: for bf16, groups that are all zero, non-finite, or have a largest magnitude of at least 2^-100
-(below that, decoded values reach bf16's subnormals, where fp32 flush modes differ between machines); for fp16, every
-group. The generators below produce no group outside that, and the tests assert so before they compare."""
+Two kinds of input. The random ones (normal deviates times a per-group power of two, through every block size, region count
+and id count of the copy kernels' matrix) stay inside what _assert_covered states: bf16 groups that are all zero, non-finite
+or have a largest magnitude of at least 2^-100, and every fp16 group. The enumerations (tests/kvc_mx_exact.py, the ones
+tests/test_kv_codec.py runs on the CPU) are the codec's whole input space: all 256 x 256 (scale byte, code) pairs through
+the decoder in four layouts, and through the encoder every magnitude pattern of both signs under every scale byte the
+encoder can write, every finite pattern as a group's lone non-zero element, and every infinity and NaN pattern. There
+every position is compared by bit pattern, bf16 subnormals and the clamped scale byte 0 included (the library is built
+with fp32 denormals kept, which is a property of its build and not of the machine), with one exception: a NaN code (0x7F or
+0xFF) under a scale byte other than 0xFF is never written by the encoder and decodes to a NaN of unspecified sign and
+payload, so those positions are compared by isnan only."""
 import threading
 import time
 
@@ -11,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import kvc_mx_exact as X
 import kvc_mx_ref as R
 from test_gpu_host_offload import DEV, GUARD, MiB, PAGE, N_MATRIX, _ids, _manager_setup, _pinned, _regions, lib  # noqa: F401
 
@@ -208,6 +216,131 @@ def test_special_groups(lib, dt):
     assert torch.equal(got.view(torch.int16), exp.view(torch.int16))
     nan = got.view(torch.int16)[0, 0, 64:160]
     assert (nan == R.QUIET_NAN[dt]).all()
+
+
+# ------------------------------------------------------------------ the whole input space (tests/kvc_mx_exact.py)
+class _Blocks:
+    """Two regions of 32 KiB blocks (512 groups each: two tiles, every wave, four pieces per wave) for `groups` groups."""
+    BB, REGIONS = 32 * 1024, 2
+
+    def __init__(self, lib, groups, dt):
+        self.ops, self.capi = lib
+        self.dt = dt
+        self.per_block = self.BB // 64 * self.REGIONS                       # groups of one id, over both regions
+        self.n = -(-groups // self.per_block)
+        self.views = _regions(self.ops, self.capi, self.REGIONS, (3 * self.n + 3) * self.BB)
+        self.rec = R.record_bytes(self.BB)
+        assert self.capi.codec_record_bytes(R.CODEC[dt], self.BB) == self.rec
+
+    def _padded(self, a):
+        """Whole blocks: the groups of `a`, then as many of them again from the start as the last block needs."""
+        return np.resize(a, (self.n * self.per_block,) + a.shape[1:])
+
+    def encode(self, bits, seed=1):
+        """bits [groups, 32] -> (the patterns that were encoded, padding included, and the kernel's codes and scale bytes)."""
+        bits = self._padded(bits)
+        x = X.as_tensor(bits, self.dt).reshape(self.n, self.REGIONS, self.BB // 2)
+        ids = _ids(self.n, seed)
+        idx = torch.tensor(ids, device=DEV)
+        for r, v in enumerate(self.views):
+            v.view(self.dt)[:(max(ids) + 1) * (self.BB // 2)].view(-1, self.BB // 2)[idx] = x[:, r].to(DEV)
+        torch.cuda.synchronize()
+        assert torch.equal(_selected(self.views, ids, self.BB, self.dt).view(torch.int16), x.view(torch.int16))
+        nbytes = self.n * self.REGIONS * self.rec
+        host = _pinned(nbytes, 0xA5)
+        self.capi.encode_blocks_to_host(0, ids, self.BB, R.CODEC[self.dt], host.data_ptr())
+        assert (host[nbytes:] == 0xA5).all()
+        img = host[:nbytes].numpy().reshape(-1, self.rec)
+        return bits, img[:, :self.BB // 2].reshape(-1, R.GROUP).copy(), img[:, self.BB // 2:].reshape(-1).copy()
+
+    def decode(self, codes, scales, seed=2):
+        """(codes [groups, 32], scale bytes [groups]) -> (both with the padding, and the kernel's patterns [groups, 32])."""
+        codes, scales = self._padded(codes), self._padded(scales)
+        pairs = self.n * self.REGIONS
+        src = _pinned(pairs * self.rec, 0x5A)
+        src.numpy()[:pairs * self.rec] = np.concatenate([codes.reshape(pairs, -1), scales.reshape(pairs, -1)], axis=1).reshape(-1)
+        ids = [i + 1 for i in _ids(self.n, seed)]                           # even ids: not the blocks encode() reads
+        self.capi.decode_blocks_from_host(0, ids, self.BB, R.CODEC[self.dt], src.data_ptr())
+        torch.cuda.synchronize()
+        assert (src[pairs * self.rec:] == 0x5A).all()
+        return codes, scales, X.as_bits(_selected(self.views, ids, self.BB, self.dt)).reshape(-1, R.GROUP)
+
+
+def _restated_encode(bits, dt):
+    c, s = R.encode(X.as_tensor(bits, dt).reshape(-1))
+    return c.numpy(), s.numpy()
+
+
+def _differences(got, want):
+    """For an assertion's message: how many positions differ, and the first few as (position, got, want)."""
+    at = np.argwhere(got != want)
+    return len(at), [(tuple(int(i) for i in a), hex(int(got[tuple(a)])), hex(int(want[tuple(a)]))) for a in at[:8]]
+
+
+def _assert_encoded_like_the_restatement(blocks, bits, built_for=None):
+    bits, codes, scales = blocks.encode(bits)
+    want_codes, want_scales = _restated_encode(bits, blocks.dt)
+    if built_for is not None:
+        assert np.array_equal(want_scales, blocks._padded(built_for))
+    assert np.array_equal(scales, want_scales), _differences(scales, want_scales)
+    assert np.array_equal(codes, want_codes), _differences(codes, want_codes)
+    return bits, codes, scales
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=_dt_id)
+def test_decode_every_pair(lib, dt):
+    """All 256 x 256 (scale byte, code) pairs, in natural order and in three shuffles of the groups and of the codes inside
+    them, so that every pair meets different lanes, quads, pieces and waves. fp16 subnormal results (rounded by the
+    conversion instruction), overflow to infinity, bf16 subnormal results, the denormal multiplier of scale byte 0 and
+    the negative zeros (code 0x80) under every scale byte are all among them."""
+    layouts = [X.every_decode_pair(seed) for seed in (None, 1, 2, 3)]
+    codes, scales = np.concatenate([c for c, _ in layouts]), np.concatenate([s for _, s in layouts])
+    blocks = _Blocks(lib, len(scales), dt)
+    assert blocks.n * blocks.per_block == len(scales) == 4 * 2048           # no padding: each pair exactly four times
+    codes, scales, got = blocks.decode(codes, scales)
+    want = X.as_bits(R.decode(torch.from_numpy(codes), torch.from_numpy(scales), dt)).reshape(-1, R.GROUP)
+    loose = X.nan_code_positions(codes, scales)                             # NaN codes under a finite scale byte: some NaN
+    assert loose.sum() == 4 * 2 * 255
+    assert X.is_nan(got[loose], dt).all() and X.is_nan(want[loose], dt).all()
+    got, want = np.where(loose, 0, got), np.where(loose, 0, want)
+    # first the positions that no treatment of subnormal numbers can touch, then all of them
+    plain = X.exact_product_class(codes, scales, dt) & (scales != 0)[:, None] if dt == torch.bfloat16 else ~loose
+    assert np.array_equal(got[plain], want[plain]), _differences(np.where(plain, got, 0), np.where(plain, want, 0))
+    assert np.array_equal(got, want), _differences(got, want)
+    assert (got[(codes == 0x80) & (scales != 0xFF)[:, None]] == 0x8000).all()
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=_dt_id)
+def test_encode_every_element_under_every_scale(lib, dt):
+    """Per scale byte sb the encoder can write: groups that hold the largest magnitude pattern that gets sb once, in a
+    rotating slot with alternating sign, and otherwise every smaller pattern with both signs. The whole image - codes
+    and scale bytes - is the restatement's (for bf16 that includes the groups below 2^-100 and subnormal elements)."""
+    bits, built_for = X.every_element_under_every_scale(dt)
+    blocks = _Blocks(lib, len(bits), dt)
+    _assert_encoded_like_the_restatement(blocks, bits, built_for)
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=_dt_id)
+def test_encode_every_maximum(lib, dt):
+    """Every finite magnitude pattern as the lone non-zero element of a group: the scale byte and the one code."""
+    bits = X.every_maximum(dt)
+    blocks = _Blocks(lib, len(bits), dt)
+    bits, codes, scales = _assert_encoded_like_the_restatement(blocks, bits)
+    n = X.inf_pattern(dt)
+    assert np.array_equal(scales[:n], X.scale_of_every_maximum(dt)) and (np.count_nonzero(codes[:n] & 0x7F, axis=1)[1:] == 1).all()
+
+
+@pytest.mark.parametrize("dt", DTYPES, ids=_dt_id)
+def test_encode_every_non_finite_pattern(lib, dt):
+    """Every infinity and NaN pattern of both signs as the one bad element of a random finite group: scale byte 0xFF and 32
+    zero codes, which decode to 32 canonical quiet NaNs."""
+    bits = X.every_non_finite(dt)
+    assert len(bits) == {torch.bfloat16: 256, torch.float16: 2048}[dt]
+    blocks = _Blocks(lib, len(bits), dt)
+    bits, codes, scales = _assert_encoded_like_the_restatement(blocks, bits)
+    assert (scales == 0xFF).all() and not codes.any()
+    _, _, back = blocks.decode(codes, scales)
+    assert (back == R.QUIET_NAN[dt]).all()
 
 
 def test_refusals_launch_and_write_nothing(lib):
