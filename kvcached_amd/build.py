@@ -6,7 +6,7 @@ sources so that they travel to the GPU box with the repo snapshot).
   vmm_ops.<abi>.so     pybind11/torch module with the reference's `kvcached.vmm_ops` surface,
                        a thin layer over the C ABI; built with g++ against the installed torch
 
-Usage: python kvcached_amd/build.py [--force]
+Usage: python kvcached_amd/build.py [--force | --print-lib-srcs]
 """
 from __future__ import annotations
 
@@ -29,9 +29,11 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = "gfx950"
 
-LIB_SRCS = ["c_api.cpp", "kv_allocator.cpp", "gpu_context.cpp", "page_allocator.cpp", "kernels.hip", "index_kernels.hip"]
-LIB_DEPS = LIB_SRCS + ["codec_math.hpp", "common.hpp", "hip_vmm.hpp", "drm_vm.hpp", "extent_pool.hpp", "gpu_context.hpp", "kernels.hpp", "kv_allocator.hpp", "mem_info.hpp",
-                       "page_allocator.hpp", "run_scan.hpp", "../../include/kvcached_amd.h"]
+# (tools_sanitize_cpu.sh builds the same list: `python kvcached_amd/build.py --print-lib-srcs`)
+LIB_SRCS = ["c_api.cpp", "kv_allocator.cpp", "kv_selftest.cpp", "kv_regions.cpp", "kv_map_paths.cpp", "kv_lanes.cpp", "kv_share.cpp", "gpu_context.cpp",
+            "page_allocator.cpp", "kernels.hip", "index_kernels.hip"]
+LIB_DEPS = LIB_SRCS + ["codec_math.hpp", "common.hpp", "hip_vmm.hpp", "drm_vm.hpp", "extent_pool.hpp", "gpu_context.hpp", "kernels.hpp", "kv_allocator.hpp",
+                       "kv_allocator_impl.hpp", "mem_info.hpp", "page_allocator.hpp", "run_scan.hpp", "../../include/kvcached_amd.h"]
 EXT_SRCS = ["vmm_ops.cpp"]
 
 
@@ -82,4 +84,7 @@ def build_all(force: bool = False):
 
 
 if __name__ == "__main__":
-    build_all("--force" in sys.argv)
+    if "--print-lib-srcs" in sys.argv:
+        print(" ".join(LIB_SRCS))
+    else:
+        build_all("--force" in sys.argv)

@@ -1,7 +1,7 @@
 // gpu_context.cpp — per-device state of the allocator: streams, kernel launches and their timing, the physical pools
 // (ExtentPool) with their housekeeping, the alias arena and the scrub queue (pages zeroed on their way back),
 // the zero extent of compat mode (§4.2), and the TLB invalidation with its epochs (§4.3). Regions, the map/unmap hot path
-// and the registry live in kv_allocator.cpp.
+// and the registry live in kv_regions.cpp, kv_map_paths.cpp, kv_lanes.cpp and kv_allocator.cpp.
 #include "kv_allocator.hpp"
 
 #include <algorithm>

@@ -75,7 +75,7 @@ struct KvRegion {
   size_t reg_group = 1;
   std::vector<hipMemGenericAllocationHandle_t> shell, shell_group;
   bool in_full_group(size_t slot) const { return reg_group > 1 && slot / reg_group < num_slots() / reg_group; }
-  std::vector<uint64_t> mark;          // one bit per slot, all clear at rest: scratch of RunScan (kv_allocator.cpp), under the allocator's lock
+  std::vector<uint64_t> mark;          // one bit per slot, all clear at rest: scratch of RunScan (run_scan.hpp), under the allocator's lock
   std::vector<uint8_t> mapped;         // per slot: its SlotState
   size_t num_slots() const { return size / page_size; }
 };
@@ -161,7 +161,7 @@ private:
   void unmap_collect(const std::vector<Slot> &slots, Unmapped &out);
   void unmap_finish(Unmapped &u, bool may_defer_shootdown);
   void reclaimer_loop();
-  // ---- lanes (kv_allocator.cpp, "lanes"): page ids of a multi-row geometry backed, scrubbed and released as units
+  // ---- lanes (kv_lanes.cpp): page ids of a multi-row geometry backed, scrubbed and released as units
   struct Row {
     KvRegion *r;
     size_t first; // slot of page id p in this row = first + p
@@ -169,10 +169,20 @@ private:
   void setup_lanes();                                      // after the regions exist: decide, build the row table
   bool try_map_lanes(const offset_t *offsets, size_t n);   // false: nothing done, the generic path takes the call
   size_t unmap_lanes(const offset_t *offsets, size_t n, std::vector<offset_t> *others); // lanes unmapped; offsets that are not lane-backed -> others
+  // the steps the lane paths share - own lanes and a peer's, map, unmap, export and import
+  static constexpr size_t kNoPageId = (size_t)-1;
+  size_t page_id_of(offset_t off) const;                   // the page id an offset names, or kNoPageId
+  template <class F> void for_rows(size_t p, F &&f);       // f(region, slot of page id p) row by row: the per-row writes of a run
+  struct RowsSplit {                                       // what back_rows leaves for settle_batch to rewrite and invalidate
+    bool prt_dirty = false, replaced = false;
+    void *zx_dirty = nullptr;
+  };
+  int back_rows(void *bo, uint64_t j0, uint64_t k, size_t p, size_t cnt, RowsSplit &split, size_t &rows_done);
+  template <class Unmap> void undo_rows(size_t p, size_t cnt, size_t rows_done, bool settled, Unmap &&unmap);
   void cold_start_reserve(ExtentPool *pool);
   bool steal_pending(size_t page_size, Phys *out);
   size_t acquire_pages(ExtentPool *pool, size_t want, Phys *out, bool *stolen); // stolen == nullptr: may not steal_pending()
-  struct MapBatch; // the state of one map_slots() batch (kv_allocator.cpp)
+  struct MapBatch; // the state of one map_slots() batch (kv_map_paths.cpp)
   void lock_foreground(std::unique_lock<std::mutex> &lk); // mu_ with priority over the reclaimer
 
   DeviceSpec dev_;
