@@ -291,6 +291,20 @@ int kvc_encode_blocks_to_host(int64_t group_id, const int64_t *block_ids, size_t
 int kvc_decode_blocks_from_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, int codec,
                                 const void *host, void *stream, int sync);
 
+/* copy_blocks_to_host_slots / copy_blocks_from_host_slots: the four copies above with a slot table, for a pinned arena that
+ * is allocated once and filled and read slot by slot (HostBlockStore; a prefix cache evicts blocks one by one and later hits
+ * any subset of them). The arena at `host` has n_slots rows of R records, [slot][region][record], and block i's row is row
+ * slots[i] instead of row i: the record of (block i, region r) is at host + (slots[i]*R + r)*rec, with rec = block_bytes for
+ * codec 0 (the bytes themselves) and kvc_codec_record_bytes(codec, block_bytes) for KVC_CODEC_*. `host` must have room for
+ * n_slots*R*rec bytes. Any set of slots in any order goes in one call. Refusals (KVC_E_INVALID, nothing launched) and
+ * KVC_E_NO_GPU as for the entries above, through the same code, and also: a slot outside [0, n_slots), n_slots above 2^32, a
+ * duplicate slot in to_host (the writes would race). A duplicate slot in from_host is legal - one record read into two blocks;
+ * a duplicate id in from_host stays refused. */
+int kvc_copy_blocks_to_host_slots(int64_t group_id, const int64_t *block_ids, const int64_t *slots, size_t n,
+                                  size_t block_bytes, int codec, void *host, size_t n_slots, void *stream, int sync);
+int kvc_copy_blocks_from_host_slots(int64_t group_id, const int64_t *block_ids, const int64_t *slots, size_t n,
+                                    size_t block_bytes, int codec, const void *host, size_t n_slots, void *stream, int sync);
+
 /* Region bases of a group's KV tensors in map order (layer-major, K then V), for compact_blocks.
  * Returns the count; copies if cap suffices. */
 int64_t kvc_get_region_bases(int64_t group_id, void **out, int64_t cap);

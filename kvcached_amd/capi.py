@@ -134,6 +134,8 @@ SIGNATURES = {
     "kvc_codec_record_bytes": (_sz, [_int, _sz]),
     "kvc_encode_blocks_to_host": (_int, [_i64, _I64P, _sz, _sz, _int, _vp, _vp, _int]),
     "kvc_decode_blocks_from_host": (_int, [_i64, _I64P, _sz, _sz, _int, _vp, _vp, _int]),
+    "kvc_copy_blocks_to_host_slots": (_int, [_i64, _I64P, _I64P, _sz, _sz, _int, _vp, _sz, _vp, _int]),
+    "kvc_copy_blocks_from_host_slots": (_int, [_i64, _I64P, _I64P, _sz, _sz, _int, _vp, _sz, _vp, _int]),
     "kvc_expand_block_ids": (_int, [_I64P, _sz, _i64, _vp, _vp]),
     "kvc_alloc_extend_indices": (_int, [_vp, _vp, _vp, _sz, _I64P, _sz, _i64, _vp, _sz, _vp]),
     "kvc_alloc_decode_indices": (_int, [_vp, _vp, _sz, _I64P, _sz, _i64, _vp, _vp]),
@@ -306,6 +308,25 @@ def decode_blocks_from_host(group_id: int, block_ids: Sequence[int], block_bytes
     """copy_blocks_from_host from an image that encode_blocks_to_host wrote with the same codec."""
     check(lib.kvc_decode_blocks_from_host(group_id, i64_array(block_ids), len(block_ids), block_bytes, codec,
                                           host_ptr or None, stream or None, int(sync)))
+
+
+def copy_blocks_to_host_slots(group_id: int, block_ids: Sequence[int], slots: Sequence[int], block_bytes: int, codec: int,
+                              host_ptr: int, n_slots: int, stream: int = 0, sync: bool = True) -> None:
+    """Blocks `block_ids` -> rows `slots` of the pinned arena of n_slots rows at host_ptr ([slot][region][record]); codec 0:
+    the bytes themselves, else KVC_CODEC_*."""
+    if len(block_ids) != len(slots):
+        raise ValueError("block_ids and slots differ in length")
+    check(lib.kvc_copy_blocks_to_host_slots(group_id, i64_array(block_ids), i64_array(slots), len(block_ids), block_bytes,
+                                            codec, host_ptr or None, n_slots, stream or None, int(sync)))
+
+
+def copy_blocks_from_host_slots(group_id: int, block_ids: Sequence[int], slots: Sequence[int], block_bytes: int, codec: int,
+                                host_ptr: int, n_slots: int, stream: int = 0, sync: bool = True) -> None:
+    """Rows `slots` of the arena that copy_blocks_to_host_slots filled with the same codec -> blocks `block_ids`."""
+    if len(block_ids) != len(slots):
+        raise ValueError("block_ids and slots differ in length")
+    check(lib.kvc_copy_blocks_from_host_slots(group_id, i64_array(block_ids), i64_array(slots), len(block_ids), block_bytes,
+                                              codec, host_ptr or None, n_slots, stream or None, int(sync)))
 
 
 def get_region_bases(group_id: int = 0) -> List[int]:

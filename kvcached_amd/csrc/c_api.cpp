@@ -472,13 +472,15 @@ int kvc_compact_blocks(void *const *region_bases, size_t n_regions, const int64_
 namespace {
 // Host side of kvc_copy_blocks_{to,from}_host and, with a codec, of kvc_encode_blocks_to_host / kvc_decode_blocks_from_host:
 // arguments, the host buffer (pinned, 16-byte aligned, resolved to the address the GPU reaches it at), then the allocator's
-// own checks and the launch.
+// own checks and the launch. With `slots` (kvc_copy_blocks_{to,from}_host_slots), block i's row of the image is row slots[i] of
+// an arena of n_slots rows.
 int copy_blocks_host(bool to_host, int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, const void *host,
-                     void *stream, int sync, int codec = kCodecRaw) {
+                     void *stream, int sync, int codec = kCodecRaw, const int64_t *slots = nullptr, size_t n_slots = 0,
+                     bool with_slots = false) {
   return guarded([&]() -> int {
     GpuContext *ctx = KvAllocator::gpu();
     if (!ctx) throw NoGpuError("copying blocks to or from host memory needs init_kvcached on a GPU device");
-    if (n && (!block_ids || !host)) throw InvalidError("NULL argument");
+    if (n && (!block_ids || !host || (with_slots && !slots))) throw InvalidError("NULL argument");
     if (block_bytes == 0 || block_bytes % 16 != 0) throw InvalidError("block_bytes must be a positive multiple of 16");
     if (codec != kCodecRaw && codec != KVC_CODEC_MXFP8_BF16 && codec != KVC_CODEC_MXFP8_F16) throw InvalidError("unknown codec");
     if (host_record_bytes(codec, block_bytes) == 0) throw InvalidError("block_bytes must be a multiple of 1024 for this codec");
@@ -488,6 +490,17 @@ int copy_blocks_host(bool to_host, int64_t group_id, const int64_t *block_ids, s
       std::vector<int64_t> sorted(block_ids, block_ids + n);
       std::sort(sorted.begin(), sorted.end());
       if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw InvalidError("duplicate block id");
+    }
+    if (with_slots) {
+      if (n_slots > 0x100000000ull) throw InvalidError("an arena holds at most 2^32 slots");
+      for (size_t i = 0; i < n; ++i)
+        if (slots[i] < 0 || (uint64_t)slots[i] >= n_slots)
+          throw InvalidError("slot " + std::to_string(slots[i]) + " is outside the arena of " + std::to_string(n_slots) + " slots");
+      if (to_host && n > 1) { // two copies into one slot would race
+        std::vector<int64_t> sorted(slots, slots + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw InvalidError("duplicate slot");
+      }
     }
     if (n == 0) return KVC_OK;
     if (reinterpret_cast<uintptr_t>(host) % 16 != 0) throw InvalidError("host buffer is not 16-byte aligned");
@@ -502,7 +515,7 @@ int copy_blocks_host(bool to_host, int64_t group_id, const int64_t *block_ids, s
     if (attr.hostPointer) dev += static_cast<const char *>(host) - static_cast<const char *>(attr.hostPointer);
     if (reinterpret_cast<uintptr_t>(dev) % 16 != 0) throw InvalidError("host buffer is not 16-byte aligned on the device side");
     KvAllocator::global(group_id)->copy_blocks_host(to_host, block_ids, n, block_bytes, dev, static_cast<hipStream_t>(stream),
-                                                    codec);
+                                                    codec, with_slots ? slots : nullptr);
     if (sync) ctx->sync(static_cast<hipStream_t>(stream));
     return KVC_OK;
   });
@@ -534,6 +547,17 @@ int kvc_encode_blocks_to_host(int64_t group_id, const int64_t *block_ids, size_t
 int kvc_decode_blocks_from_host(int64_t group_id, const int64_t *block_ids, size_t n, size_t block_bytes, int codec,
                                 const void *host, void *stream, int sync) {
   return copy_blocks_host(false, group_id, block_ids, n, block_bytes, host, stream, sync, codec == kCodecRaw ? -1 : codec);
+}
+
+// (here codec 0 is the raw copy: one pair of entries for the three images)
+int kvc_copy_blocks_to_host_slots(int64_t group_id, const int64_t *block_ids, const int64_t *slots, size_t n, size_t block_bytes,
+                                  int codec, void *host, size_t n_slots, void *stream, int sync) {
+  return copy_blocks_host(true, group_id, block_ids, n, block_bytes, host, stream, sync, codec, slots, n_slots, true);
+}
+
+int kvc_copy_blocks_from_host_slots(int64_t group_id, const int64_t *block_ids, const int64_t *slots, size_t n,
+                                    size_t block_bytes, int codec, const void *host, size_t n_slots, void *stream, int sync) {
+  return copy_blocks_host(false, group_id, block_ids, n, block_bytes, host, stream, sync, codec, slots, n_slots, true);
 }
 
 int64_t kvc_get_region_bases(int64_t group_id, void **out, int64_t cap) {

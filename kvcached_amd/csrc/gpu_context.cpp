@@ -580,13 +580,19 @@ void GpuContext::compact(void *const *bases, size_t n_regions, const int64_t *sr
 }
 
 void GpuContext::copy_blocks_host(bool to_host, void *const *bases, size_t n_regions, const int64_t *ids, size_t n,
-                                  size_t block_bytes, void *host, hipStream_t s, int codec) {
+                                  size_t block_bytes, void *host, hipStream_t s, int codec, const int64_t *slots) {
   if (!s) s = stream_;
   const size_t record = host_record_bytes(codec, block_bytes); // (the callers have refused a codec that gives 0)
+  const size_t per_launch = slots ? kMaxSlotIdsPerLaunch : kMaxIdsPerLaunch;
   for (size_t r = 0; r < n_regions; r += kMaxRegionsPerLaunch) {
     const int nr = (int)std::min<size_t>(kMaxRegionsPerLaunch, n_regions - r);
-    for (size_t i = 0; i < n; i += kMaxIdsPerLaunch) {
-      const int ni = (int)std::min<size_t>(kMaxIdsPerLaunch, n - i);
+    for (size_t i = 0; i < n; i += per_launch) {
+      const int ni = (int)std::min<size_t>(per_launch, n - i);
+      if (slots) { // the rows are named by the table: `host` is the arena itself
+        HIP_CHECK(launch_copy_blocks_host_slots(to_host, bases + r, nr, (int)r, (int)n_regions, ids + i, slots + i, ni,
+                                                block_bytes, host, s, codec));
+        continue;
+      }
       char *h = static_cast<char *>(host) + i * n_regions * record; // row i of the image
       HIP_CHECK(launch_copy_blocks_host(to_host, bases + r, nr, (int)r, (int)n_regions, ids + i, ni, block_bytes, h, s, codec));
     }

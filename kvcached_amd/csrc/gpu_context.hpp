@@ -113,9 +113,10 @@ public:
   void compact(void *const *bases, size_t n_regions, const int64_t *src, const int64_t *dst, size_t n_moves,
                size_t block_bytes, hipStream_t s);
   // blocks <-> a block-major host image (copy_blocks_to_host / _from_host, or encode_ / decode_ with a codec: HostCodec of
-  // kernels.hpp); `host` is a device address of pinned memory
+  // kernels.hpp); `host` is a device address of pinned memory. With `slots`, block i's row of the image is row slots[i] of
+  // the arena at `host` (launch_copy_blocks_host_slots) instead of row i.
   void copy_blocks_host(bool to_host, void *const *bases, size_t n_regions, const int64_t *ids, size_t n, size_t block_bytes,
-                        void *host, hipStream_t s, int codec = 0);
+                        void *host, hipStream_t s, int codec = 0, const int64_t *slots = nullptr);
   void sync(hipStream_t s); // hipStreamSynchronize + harvest event timings
   // ---- zeroing pages on their way BACK (drm backend, extents with an alias mapping).
   // A page handed out by map_slots must read zero. Filling it there puts 0.3 us per page of GPU time between the

@@ -370,6 +370,17 @@ struct HostCopyArgs {
   int64_t id[kMaxIdsPerLaunch];
 };
 static_assert(sizeof(HostCopyArgs) <= 12 * 1024, "kernarg segment budget");
+// The same with a slot table (launch_copy_blocks_host_slots): block i's row of the host image is row slot[i] of a pinned arena
+// (HostBlockStore), not row i. 32-bit slots: the row's byte offset is formed in 64 bits, and 2^32 rows are more than any host has.
+struct HostSlotArgs {
+  void *base[kMaxRegionsPerLaunch];
+  int64_t id[kMaxSlotIdsPerLaunch];
+  uint32_t slot[kMaxSlotIdsPerLaunch];
+};
+static_assert(sizeof(HostSlotArgs) <= 12 * 1024, "kernarg segment budget");
+// The row of the host image that holds block i of the launch (one more scalar load per workgroup with a slot table).
+__device__ __forceinline__ size_t host_row(const HostCopyArgs &, unsigned i) { return i; }
+__device__ __forceinline__ size_t host_row(const HostSlotArgs &a, unsigned i) { return a.slot[i]; }
 
 // Which (block, region) pair and which tile of it this workgroup has: the device address of the tile, the index of the pair's
 // record in the host image, and the tile number. Tile-fastest, then region, then block.
@@ -378,15 +389,16 @@ struct HostTile {
   size_t record;
   unsigned t;
 };
-__device__ __forceinline__ HostTile host_tile(const HostCopyArgs &a, unsigned n_regions, unsigned region0, unsigned row_regions,
+template <class Args>
+__device__ __forceinline__ HostTile host_tile(const Args &a, unsigned n_regions, unsigned region0, unsigned row_regions,
                                               unsigned tiles, unsigned block_bytes) {
   const unsigned pair = blockIdx.x / tiles, t = blockIdx.x - pair * tiles;
   const unsigned i = pair / n_regions, r = pair - i * n_regions;
-  return {tile_address<kTile16>(a.base[r], a.id[i], block_bytes, t), (size_t)i * row_regions + region0 + r, t};
+  return {tile_address<kTile16>(a.base[r], a.id[i], block_bytes, t), host_row(a, i) * row_regions + region0 + r, t};
 }
 
-template <bool TO_HOST>
-__device__ __forceinline__ void copy_blocks_host_tile(const HostCopyArgs &a, char *host, unsigned n_regions, unsigned region0,
+template <bool TO_HOST, class Args>
+__device__ __forceinline__ void copy_blocks_host_tile(const Args &a, char *host, unsigned n_regions, unsigned region0,
                                                       unsigned row_regions, unsigned tiles, unsigned block_bytes) {
   const HostTile w = host_tile(a, n_regions, region0, row_regions, tiles, block_bytes);
   char *hst = host + w.record * block_bytes + (size_t)w.t * kTile16;
@@ -404,6 +416,18 @@ __global__ __launch_bounds__(kCopyThreads) void copy_blocks_to_host_kernel(HostC
 __global__ __launch_bounds__(kCopyThreads) void copy_blocks_from_host_kernel(HostCopyArgs a, char *host, unsigned n_regions,
                                                                               unsigned region0, unsigned row_regions,
                                                                               unsigned tiles, unsigned block_bytes) {
+  copy_blocks_host_tile<false>(a, host, n_regions, region0, row_regions, tiles, block_bytes);
+}
+
+__global__ __launch_bounds__(kCopyThreads) void copy_blocks_to_host_slots_kernel(HostSlotArgs a, char *host, unsigned n_regions,
+                                                                                  unsigned region0, unsigned row_regions,
+                                                                                  unsigned tiles, unsigned block_bytes) {
+  copy_blocks_host_tile<true>(a, host, n_regions, region0, row_regions, tiles, block_bytes);
+}
+
+__global__ __launch_bounds__(kCopyThreads) void copy_blocks_from_host_slots_kernel(HostSlotArgs a, char *host, unsigned n_regions,
+                                                                                    unsigned region0, unsigned row_regions,
+                                                                                    unsigned tiles, unsigned block_bytes) {
   copy_blocks_host_tile<false>(a, host, n_regions, region0, row_regions, tiles, block_bytes);
 }
 
@@ -431,8 +455,8 @@ __device__ __forceinline__ unsigned quad_max(unsigned x) { // the maximum over t
 // Half16<F16>, e4m3_magnitude_code and e4m3_magnitude - the steps without lane intrinsics - are in codec_math.hpp, which also
 // compiles as plain C++ so that the tests can enumerate them on the CPU.
 
-template <bool F16, bool TO_HOST>
-__device__ __forceinline__ void codec_blocks_host_tile(const HostCopyArgs &a, char *host, unsigned n_regions, unsigned region0,
+template <bool F16, bool TO_HOST, class Args>
+__device__ __forceinline__ void codec_blocks_host_tile(const Args &a, char *host, unsigned n_regions, unsigned region0,
                                                        unsigned row_regions, unsigned tiles, unsigned block_bytes) {
   using H = Half16<F16>;
   const HostTile w = host_tile(a, n_regions, region0, row_regions, tiles, block_bytes);
@@ -514,15 +538,19 @@ __device__ __forceinline__ void codec_blocks_host_tile(const HostCopyArgs &a, ch
 }
 
 // (named kernels, as above: a profile names the direction and the element type)
-#define KVC_CODEC_KERNEL(name, F16, TO_HOST)                                                                                  \
-  __global__ __launch_bounds__(kCopyThreads) void name(HostCopyArgs a, char *host, unsigned n_regions, unsigned region0,       \
+#define KVC_CODEC_KERNEL(name, Args, F16, TO_HOST)                                                                            \
+  __global__ __launch_bounds__(kCopyThreads) void name(Args a, char *host, unsigned n_regions, unsigned region0,               \
                                                        unsigned row_regions, unsigned tiles, unsigned block_bytes) {           \
     codec_blocks_host_tile<F16, TO_HOST>(a, host, n_regions, region0, row_regions, tiles, block_bytes);                        \
   }
-KVC_CODEC_KERNEL(encode_blocks_to_host_bf16_kernel, false, true)
-KVC_CODEC_KERNEL(encode_blocks_to_host_f16_kernel, true, true)
-KVC_CODEC_KERNEL(decode_blocks_from_host_bf16_kernel, false, false)
-KVC_CODEC_KERNEL(decode_blocks_from_host_f16_kernel, true, false)
+KVC_CODEC_KERNEL(encode_blocks_to_host_bf16_kernel, HostCopyArgs, false, true)
+KVC_CODEC_KERNEL(encode_blocks_to_host_f16_kernel, HostCopyArgs, true, true)
+KVC_CODEC_KERNEL(decode_blocks_from_host_bf16_kernel, HostCopyArgs, false, false)
+KVC_CODEC_KERNEL(decode_blocks_from_host_f16_kernel, HostCopyArgs, true, false)
+KVC_CODEC_KERNEL(encode_blocks_to_host_slots_bf16_kernel, HostSlotArgs, false, true)
+KVC_CODEC_KERNEL(encode_blocks_to_host_slots_f16_kernel, HostSlotArgs, true, true)
+KVC_CODEC_KERNEL(decode_blocks_from_host_slots_bf16_kernel, HostSlotArgs, false, false)
+KVC_CODEC_KERNEL(decode_blocks_from_host_slots_f16_kernel, HostSlotArgs, true, false)
 #undef KVC_CODEC_KERNEL
 
 hipError_t launch_copy_blocks_host(bool to_host, void *const *bases, int n_regions, int region0, int row_regions,
@@ -546,6 +574,35 @@ hipError_t launch_copy_blocks_host(bool to_host, void *const *bases, int n_regio
   static const HostKernel kernels[3][2] = {{copy_blocks_from_host_kernel, copy_blocks_to_host_kernel},
                                            {decode_blocks_from_host_bf16_kernel, encode_blocks_to_host_bf16_kernel},
                                            {decode_blocks_from_host_f16_kernel, encode_blocks_to_host_f16_kernel}};
+  kernels[codec][to_host ? 1 : 0]<<<dim3((unsigned)grid), dim3(kCopyThreads), 0, stream>>>(
+      a, static_cast<char *>(host), (unsigned)n_regions, (unsigned)region0, (unsigned)row_regions, tiles, (unsigned)block_bytes);
+  return hipGetLastError();
+}
+
+// The slot-table form: the checks of the launcher above, and a slot that fits the table's 32 bits.
+hipError_t launch_copy_blocks_host_slots(bool to_host, void *const *bases, int n_regions, int region0, int row_regions,
+                                         const int64_t *ids, const int64_t *slots, int n, size_t block_bytes, void *host,
+                                         hipStream_t stream, int codec) {
+  if (n_regions <= 0 || n <= 0) return hipSuccess;
+  if (n_regions > kMaxRegionsPerLaunch || n > kMaxSlotIdsPerLaunch || region0 < 0 || row_regions < region0 + n_regions ||
+      block_bytes == 0 || block_bytes % 16 != 0 || block_bytes > 0x7fffffffull || reinterpret_cast<uintptr_t>(host) % 16 != 0 ||
+      host_record_bytes(codec, block_bytes) == 0)
+    return hipErrorInvalidValue;
+  HostSlotArgs a;
+  if (!copy_bases(a.base, bases, n_regions)) return hipErrorInvalidValue;
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || slots[i] < 0 || slots[i] > 0xffffffffll) return hipErrorInvalidValue;
+    a.id[i] = ids[i];
+    a.slot[i] = (uint32_t)slots[i];
+  }
+  const unsigned tiles = (unsigned)((block_bytes + kTile16 - 1) / kTile16);
+  const size_t grid = (size_t)tiles * (size_t)n * (size_t)n_regions;
+  if (grid > 0x7fffffffull) return hipErrorInvalidValue;
+  // rows and columns as in launch_copy_blocks_host
+  using SlotKernel = void (*)(HostSlotArgs, char *, unsigned, unsigned, unsigned, unsigned, unsigned);
+  static const SlotKernel kernels[3][2] = {{copy_blocks_from_host_slots_kernel, copy_blocks_to_host_slots_kernel},
+                                           {decode_blocks_from_host_slots_bf16_kernel, encode_blocks_to_host_slots_bf16_kernel},
+                                           {decode_blocks_from_host_slots_f16_kernel, encode_blocks_to_host_slots_f16_kernel}};
   kernels[codec][to_host ? 1 : 0]<<<dim3((unsigned)grid), dim3(kCopyThreads), 0, stream>>>(
       a, static_cast<char *>(host), (unsigned)n_regions, (unsigned)region0, (unsigned)row_regions, tiles, (unsigned)block_bytes);
   return hipGetLastError();

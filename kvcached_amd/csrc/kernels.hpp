@@ -16,6 +16,7 @@ static constexpr int kMaxPtrsPerLaunch = 1024; // 8 KiB of kernarg: a whole 1024
 static constexpr int kMaxRegionsPerLaunch = 128;
 static constexpr int kMaxMovesPerLaunch = 448; // 448 x 16 B + 128 x 8 B = 8 KiB of kernarg (32 KiB / 1984 moves per launch was tried in round 3: fewer launches, but no faster on 32 KiB blocks and 8-10 % slower on 16-18 KiB blocks - every workgroup reads its three entries through the scalar cache)
 static constexpr int kMaxIdsPerLaunch = 1024; // block ids one index-kernel launch carries in its kernarg (8 KiB)
+static constexpr int kMaxSlotIdsPerLaunch = 768; // (block id, host slot) pairs of one slot-table host copy: 768 x (8 + 4) B + 128 x 8 B = 10 KiB of kernarg
 
 // Zero `n` pages of `page_bytes` each (n <= kMaxPtrsPerLaunch). Asynchronous on `stream`.
 // variant: 0 = default; the others are tuning variants kept for A/B runs (kFillVariants in kernels.hip is the list).
@@ -48,6 +49,14 @@ inline size_t host_record_bytes(int codec, size_t block_bytes) {
 hipError_t launch_copy_blocks_host(bool to_host, void *const *bases, int n_regions, int region0, int row_regions,
                                    const int64_t *ids, int n, size_t block_bytes, void *host, hipStream_t stream,
                                    int codec = kCodecRaw);
+
+// The same copies with a slot table: block i's row of the image is row slots[i] of a pinned arena, not row i:
+//   host + ((slots[i] * row_regions + region0 + r) * record)  <->  bases[r] + ids[i]*block_bytes
+// n <= kMaxSlotIdsPerLaunch, 0 <= slots[i] < 2^32 (the kernarg carries 32-bit slots; host offsets are formed in 64 bits);
+// everything else as above. Two blocks on one slot race when to_host: the caller refuses that.
+hipError_t launch_copy_blocks_host_slots(bool to_host, void *const *bases, int n_regions, int region0, int row_regions,
+                                         const int64_t *ids, const int64_t *slots, int n, size_t block_bytes, void *host,
+                                         hipStream_t stream, int codec = kCodecRaw);
 
 // One lane: optionally store `value` to *p, then copy *p to *out_dev (the TLB self test's view of memory).
 hipError_t launch_peek_poke(void *p, unsigned *out_dev, unsigned value, bool do_write, hipStream_t stream);

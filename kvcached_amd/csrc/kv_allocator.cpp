@@ -455,7 +455,7 @@ std::vector<void *> KvAllocator::region_bases() {
 }
 
 void KvAllocator::copy_blocks_host(bool to_host, const int64_t *ids, size_t n, size_t block_bytes, void *host, hipStream_t s,
-                                   int codec) {
+                                   int codec, const int64_t *slots) {
   if (!ctx_) throw NoGpuError("copying blocks to or from host memory needs init_kvcached on a GPU device");
   std::unique_lock<std::mutex> g(mu_, std::defer_lock);
   lock_foreground(g);
@@ -491,7 +491,7 @@ void KvAllocator::copy_blocks_host(bool to_host, const int64_t *ids, size_t n, s
     }
   }
   ctx_->bind();
-  ctx_->copy_blocks_host(to_host, bases.data(), bases.size(), ids, n, block_bytes, host, s, codec);
+  ctx_->copy_blocks_host(to_host, bases.data(), bases.size(), ids, n, block_bytes, host, s, codec, slots);
 }
 
 // Offsets -> (region, slot) in the reference's order: layer-major, then offset, K before V

@@ -108,7 +108,9 @@ public:
   // (device address of pinned host memory). Under the lock, every slot a (block, region) byte range touches must be backed
   // (Own, Imported, Lane, PeerLane), else InvalidError and nothing is launched; the launch is issued under the lock too.
   // codec: 0 = the bytes themselves, else the KVC_CODEC_* number of the image's encoding (the caller has checked it).
-  void copy_blocks_host(bool to_host, const int64_t *ids, size_t n, size_t block_bytes, void *host, hipStream_t s, int codec = 0);
+  // slots (optional): block i goes to / comes from row slots[i] of the arena at `host` (the caller has checked the slots).
+  void copy_blocks_host(bool to_host, const int64_t *ids, size_t n, size_t block_bytes, void *host, hipStream_t s, int codec = 0,
+                        const int64_t *slots = nullptr);
   bool uses_prt();                    // unbacked slots of this group's regions are PRT mappings
   size_t lanes_per_extent();          // page ids are backed by lanes: lanes a buffer holds at most (0: per-slot pages)
 

@@ -18,7 +18,9 @@ Order-defining rules that the golden traces pin (reference line numbers):
 Additions (not in the reference, off unless called): `compact()` — plans and executes, with the
 compact_blocks HIP kernel, the block moves that empty sparsely used pages so they can be unmapped;
 `offload()` / `restore()` — copy live blocks to pinned host memory and free them, and later bring
-them back under new ids (copy_blocks_to_host / copy_blocks_from_host HIP kernels).
+them back under new ids (copy_blocks_to_host / copy_blocks_from_host HIP kernels); `offload_to()` /
+`restore_from()` — the same into and out of single slots of a HostBlockStore (kvcached_amd/host_store.py), a
+pinned arena that is allocated once.
 """
 from __future__ import annotations
 
@@ -603,6 +605,67 @@ class KVCacheManager:
             self.free(new_ids)
             raise
         handle._record()
+        return new_ids
+
+    def _check_store(self, store: "HostBlockStore") -> int:
+        """Block bytes of this manager, after the refusals offload_to / restore_from share."""
+        self._wait_post_init()
+        if self._kv_remote:
+            raise RuntimeError("a host store needs the KV tensors in this process (world_size == 1, no worker IPC); "
+                               "offload under tensor parallelism is not supported")
+        store._check_open()
+        bases, block_bytes = self._block_geometry()
+        key = self._geometry_key(len(bases), block_bytes)
+        if store.geometry != key:
+            raise ValueError(f"a host store of geometry {store.geometry} (group, contiguous, regions, block bytes) "
+                             f"cannot hold blocks of {key}")
+        return block_bytes
+
+    @synchronized
+    def offload_to(self, store: "HostBlockStore", block_ids: List[int]) -> Optional[List[int]]:
+        """offload() into free slots of a HostBlockStore: copy live blocks there on torch.cuda.current_stream(), wait
+        until the bytes are there, and free the blocks. Returns the slots, in the order of block_ids (slots[i] holds
+        block_ids[i]), or None (nothing changed) when the store has too few free slots. Raises what offload() raises, and
+        ValueError for a store of another geometry; any error leaves the store and the manager as they were."""
+        block_bytes = self._check_store(store)
+        ids = [int(b) for b in block_ids]
+        self._check_live_blocks(ids)
+        from kvcached_amd import capi
+        slots = store._take(len(ids))
+        if slots is None:
+            return None
+        try:
+            _on_current_stream(lambda s: capi.copy_blocks_to_host_slots(self.group_id, ids, slots, block_bytes, store.codec_id,
+                                                                        store.data.data_ptr(), store.capacity, s, sync=True))
+        except BaseException:
+            store._give_back(slots)
+            raise
+        self.free(ids)   # only now: free() may unmap pages, and the copy has read them
+        return slots
+
+    @synchronized
+    def restore_from(self, store: "HostBlockStore", slots: List[int]) -> Optional[List[int]]:
+        """Allocate len(slots) blocks and queue ONE gather of those slots into them on torch.cuda.current_stream():
+        new_ids[i] holds slot slots[i] (a slot may be named twice). Not waited for: later work on that stream sees the
+        data, and store.free() keeps a freed slot back until the copy is over. Returns None (nothing changed) when the
+        pool cannot hold them; ValueError for a store of another geometry or a slot that is not in use. The slots stay
+        valid and can be restored again."""
+        block_bytes = self._check_store(store)
+        slots = store._check_in_use(slots, "restore_from")
+        if not slots:
+            raise ValueError("restore_from needs at least one slot")
+        from kvcached_amd import capi
+        new_ids = self.alloc(len(slots))
+        if new_ids is None:
+            return None
+        try:
+            _on_current_stream(lambda s: capi.copy_blocks_from_host_slots(self.group_id, new_ids, slots, block_bytes,
+                                                                          store.codec_id, store.data.data_ptr(),
+                                                                          store.capacity, s, sync=False))
+        except Exception:
+            self.free(new_ids)
+            raise
+        store._record()
         return new_ids
 
 
