@@ -4,18 +4,26 @@ from __future__ import annotations
 import numpy as np
 
 
-def extend_case(seed: int, bs: int, tpb: int, max_prefix: int, max_extend: int, n_blocks: int = 1 << 20,
-                aligned_prefix: bool = False, zero_extend_every: int = 0, id_base: int = 0):
+def extend_case(seed: int, bs: int, tpb: int, max_prefix: int = None, max_extend: int = None, n_blocks: int = 1 << 20,
+                aligned_prefix: bool = False, zero_extend_every: int = 0, id_base: int = 0, prefix_lens=None, extend_lens=None):
     """A consistent alloc_extend input: each request owns distinct blocks for its prefix; last_loc is the slot of
     its last prefix token (-1 when the prefix is empty, as SGLang passes it). `id_base` is added to every drawn block id
-    (token indices of 2^31, 2^32 and beyond; the default leaves the cases as they always were)."""
+    (token indices of 2^31, 2^32 and beyond; the default leaves the cases as they always were). `prefix_lens` and
+    `extend_lens` (both or neither, bs entries each) take the place of the drawn lengths: only the block ids are drawn then."""
     rng = np.random.default_rng(seed)
-    pre = rng.integers(0, max_prefix + 1, size=bs)
-    if aligned_prefix:
-        pre = pre // tpb * tpb
-    ext = rng.integers(1, max_extend + 1, size=bs)
-    if zero_extend_every:
-        ext[::zero_extend_every] = 0
+    drawn = max_prefix is not None and max_extend is not None and prefix_lens is None and extend_lens is None
+    given = max_prefix is None and max_extend is None and prefix_lens is not None and extend_lens is not None
+    assert drawn or given, "give either max_prefix and max_extend or prefix_lens and extend_lens"
+    if drawn:
+        pre = rng.integers(0, max_prefix + 1, size=bs)
+        if aligned_prefix:
+            pre = pre // tpb * tpb
+        ext = rng.integers(1, max_extend + 1, size=bs)
+        if zero_extend_every:
+            ext[::zero_extend_every] = 0
+    else:
+        pre, ext = np.array(prefix_lens, dtype=np.int64), np.array(extend_lens, dtype=np.int64)
+        assert pre.shape == ext.shape == (bs,) and (pre >= 0).all() and (ext >= 0).all()
     seq = pre + ext
     pre_blocks = (pre + tpb - 1) // tpb
     new_blocks = (seq + tpb - 1) // tpb - pre_blocks
@@ -30,12 +38,18 @@ def extend_case(seed: int, bs: int, tpb: int, max_prefix: int, max_extend: int, 
                 free_pages=free_pages, tpb=tpb, owned=owned, extend_num_tokens=int(ext.sum()))
 
 
-def decode_case(seed: int, bs: int, tpb: int, max_len: int, n_blocks: int = 1 << 20, force_boundary_every: int = 0,
-                id_base: int = 0):
+def decode_case(seed: int, bs: int, tpb: int, max_len: int = None, n_blocks: int = 1 << 20, force_boundary_every: int = 0,
+                id_base: int = 0, seq_lens=None):
+    """`seq_lens` (bs entries, each >= 1) takes the place of the drawn lengths: only the block ids are drawn then."""
     rng = np.random.default_rng(seed)
-    seq = rng.integers(1, max_len + 1, size=bs)
-    if force_boundary_every:
-        seq[::force_boundary_every] = (seq[::force_boundary_every] // tpb) * tpb + 1
+    assert (max_len is None) != (seq_lens is None), "give either max_len or seq_lens"
+    if seq_lens is None:
+        seq = rng.integers(1, max_len + 1, size=bs)
+        if force_boundary_every:
+            seq[::force_boundary_every] = (seq[::force_boundary_every] // tpb) * tpb + 1
+    else:
+        seq = np.array(seq_lens, dtype=np.int64)
+        assert seq.shape == (bs,) and (seq >= 1).all()
     pre = seq - 1
     pre_blocks = (pre + tpb - 1) // tpb
     need = (seq + tpb - 1) // tpb - pre_blocks

@@ -47,7 +47,8 @@ def test_expand_block_ids(gpu_lib, n, tpb):
 
 
 EXTEND_GPU_CASES = G.EXTEND_CASES + [
-    dict(seed=11, bs=1, tpb=16, max_prefix=5, max_extend=20000),           # one long prompt: several token groups
+    dict(seed=11, bs=1, tpb=16, max_prefix=5, max_extend=20000),           # one prompt of 2572 tokens: ONE token group (the seams
+    #                                                                        of the groups: tests/test_gpu_index_edges.py)
     dict(seed=12, bs=700, tpb=16, max_prefix=64, max_extend=64),           # > 256 requests: strided prefix sums
     dict(seed=13, bs=40, tpb=16, max_prefix=200, max_extend=2000),         # > 1024 new blocks: staged id table
     dict(seed=14, bs=2000, tpb=1, max_prefix=3, max_extend=3),             # page_size 1
