@@ -118,7 +118,7 @@ def elastic_pass(rate: float, duration: float, seed: int = 1, passes: int = 2):
 def _replay(capi, m, ops, rate, duration, num_blocks, startup):
     time.sleep(0.3)                  # let the prealloc thread fill the reserved pool
     capi.reset_stats()
-    c0 = [int(capi.get_option(k)) for k in (112, 113, 114, 115)]
+    c0 = [int(capi.get_option(k)) for k in (capi.OPT_KFD_ALLOC_NS, capi.OPT_KFD_EXPORT_NS, capi.OPT_DRM_IMPORT_NS, capi.OPT_KFD_CREATES)]
     live, lat_a, lat_f, none_count = {}, [], [], 0
     peak_pages, sum_pages = 0, 0
     pa = m.page_allocator
@@ -147,7 +147,7 @@ def _replay(capi, m, ops, rate, duration, num_blocks, startup):
     m.trim()
     capi.flush_unmaps()
     st = capi.get_stats()
-    c1 = [int(capi.get_option(k)) for k in (112, 113, 114, 115)]
+    c1 = [int(capi.get_option(k)) for k in (capi.OPT_KFD_ALLOC_NS, capi.OPT_KFD_EXPORT_NS, capi.OPT_DRM_IMPORT_NS, capi.OPT_KFD_CREATES)]
     n_created = max(1, c1[3] - c0[3])
     mapped = max(st["pages_mapped"], 1)
     unit = PAGE * L * 2
@@ -169,9 +169,9 @@ def _replay(capi, m, ops, rate, duration, num_blocks, startup):
            "pool_GiB_virtual": round(num_blocks * BLOCK * CELL * L * 2 / 2**30, 1), "startup_s": round(startup, 3),
            "tlb_shootdowns": st["tlb_shootdowns"],
            "page_ids_per_map_call": round(st["pages_mapped"] / (2 * L) / max(st["map_calls"], 1), 2),
-           "lanes_per_buffer": int(capi.get_option(129)),
-           "host_us_per_2MiB_mapped": {name: round(int(capi.get_option(130 + i)) / 1e3 / mapped, 3) for i, name in SEGMENTS.items()
-                                       if int(capi.get_option(130 + i))},
+           "lanes_per_buffer": int(capi.get_option(capi.OPT_LANES_PER_BUFFER)),
+           "host_us_per_2MiB_mapped": {name: round(int(capi.get_option(capi.OPT_HOST_SEGMENT_0 + i)) / 1e3 / mapped, 3) for i, name in SEGMENTS.items()
+                                       if int(capi.get_option(capi.OPT_HOST_SEGMENT_0 + i))},
            "buffers_created": c1[3] - c0[3],
            "create_us_per_buffer": {"kfd_alloc": round((c1[0] - c0[0]) / n_created / 1e3, 1), "export": round((c1[1] - c0[1]) / n_created / 1e3, 1),
                                     "drm_import": round((c1[2] - c0[2]) / n_created / 1e3, 1)} if c1[3] > c0[3] else None}

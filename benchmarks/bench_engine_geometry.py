@@ -54,7 +54,7 @@ def run(capi, n_ids, placement, iters, half_slots, layers, rng):
         capi.unmap_from_kv_tensors(offs)
     capi.flush_unmaps()
     capi.reset_stats()
-    c0 = int(capi.get_option(115))
+    c0 = int(capi.get_option(capi.OPT_KFD_CREATES))
     tm, tu = [], []
     for it in range(iters):
         arr = capi.i64_array([p * PAGE for p in ids_for(it)])
@@ -68,8 +68,8 @@ def run(capi, n_ids, placement, iters, half_slots, layers, rng):
     capi.flush_unmaps()
     st = capi.get_stats()
     slots = n_ids * layers * 2
-    seg = {name: round(int(capi.get_option(130 + i)) / 1e3 / iters, 1) for i, name in SEG.items()}
-    cnt = {name: round(int(capi.get_option(130 + i)) / iters, 1) for i, name in COUNTS.items()}
+    seg = {name: round(int(capi.get_option(capi.OPT_HOST_SEGMENT_0 + i)) / 1e3 / iters, 1) for i, name in SEG.items()}
+    cnt = {name: round(int(capi.get_option(capi.OPT_HOST_SEGMENT_0 + i)) / iters, 1) for i, name in COUNTS.items()}
     p50m, p50u = statistics.median(tm), statistics.median(tu)
     return {"page_ids": n_ids, "placement": placement, "slots_2MiB": slots,
             "map_ms": {"p50": round(p50m * 1e3, 3), "p90": round(sorted(tm)[int(.9 * (len(tm) - 1))] * 1e3, 3), "max": round(max(tm) * 1e3, 3)},
@@ -80,7 +80,7 @@ def run(capi, n_ids, placement, iters, half_slots, layers, rng):
             "host_us_per_call": {k: v for k, v in seg.items() if v},
             "per_call": cnt, "tlb_shootdowns_per_cycle": round(st["tlb_shootdowns"] / iters, 2),
             "shootdown_us": round(st["shootdown_ns"] / 1e3 / max(1, st["tlb_shootdowns"]), 1),
-            "driver_allocations_in_timed_region": int(capi.get_option(115)) - c0,
+            "driver_allocations_in_timed_region": int(capi.get_option(capi.OPT_KFD_CREATES)) - c0,
             "handles_created": st["handles_created"], "handles_reused": st["handles_reused"]}
 
 
@@ -105,8 +105,8 @@ def main():
     capi.init("cuda:0", PAGE, False)
     capi.create_kv_tensors(2 * args.half_slots * PAGE, 1, "cuda:0", args.layers, 2, 0, False)
     print(json.dumps({"startup_s": round(time.perf_counter() - t0, 3), "mode": args.mode, "layers": args.layers,
-                      "VA_GiB": 2 * args.half_slots * PAGE * args.layers / 2**30, "prt": int(capi.get_option(128)),
-                      "max_extent_pages": int(capi.get_option(119))}), flush=True)
+                      "VA_GiB": 2 * args.half_slots * PAGE * args.layers / 2**30, "prt": int(capi.get_option(capi.OPT_PRT)),
+                      "max_extent_pages": int(capi.get_option(capi.OPT_MAX_EXTENT_PAGES))}), flush=True)
     rng = np.random.default_rng(0)
     try:
         for placement in args.placements.split(","):

@@ -35,9 +35,9 @@ def main():
     os.environ["KVCACHED_PHYS_POOL_MB"] = "0"            # every unmap gives the page back to the driver
     os.environ["KVCACHED_PHYS_CHUNK_PAGES"] = str(args.chunk)
     os.environ.setdefault("KVCACHED_LOG_LEVEL", "ERROR")
-    lib = ctypes.CDLL(os.path.join(REPO, "kvcached_amd", "libkvcached_amd.so"), mode=ctypes.RTLD_GLOBAL)
-    lib.kvc_get_option.restype = ctypes.c_int64
-    lib.kvc_last_error.restype = ctypes.c_char_p
+    sys.path.insert(0, REPO)
+    from kvcached_amd import capi   # (after the environment is set: the library reads it at kvc_init)
+    lib = capi.lib
 
     def ck(rc):
         if rc < 0:
@@ -51,14 +51,15 @@ def main():
     f, t = ctypes.c_size_t(), ctypes.c_size_t()
     lib.kvc_mem_get_info(ctypes.byref(f), ctypes.byref(t))
     print(json.dumps({"phase": "start", "free_GiB": round(f.value / 2**30, 1), "total_GiB": round(t.value / 2**30, 1),
-                      "kfd_create": int(lib.kvc_get_option(110)), "backend": int(lib.kvc_get_option(108)),
+                      "kfd_create": int(lib.kvc_get_option(capi.OPT_KFD_CREATE_ACTIVE)), "backend": int(lib.kvc_get_option(capi.OPT_EFFECTIVE_BACKEND)),
                       "chunk_pages": args.chunk}), flush=True)
 
     def offs(b):
         return (ctypes.c_int64 * N)(*[(b * N + i) * PAGE for i in range(N)])
 
     def opts():
-        return [int(lib.kvc_get_option(k)) for k in (112, 113, 114, 115, 116, 117)]
+        return [int(lib.kvc_get_option(k)) for k in (capi.OPT_KFD_ALLOC_NS, capi.OPT_KFD_EXPORT_NS, capi.OPT_DRM_IMPORT_NS, capi.OPT_KFD_CREATES,
+                                                   capi.OPT_KFD_FREE_NS, capi.OPT_KFD_FREES)]
 
     def run(phase, first, n, unmap=False):
         o0 = opts()

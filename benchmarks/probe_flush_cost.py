@@ -35,7 +35,7 @@ def child(args):
     window = args.window_gib * 512 // N                 # batches of 1024 pages
     capi.create_kv_tensors(window * N * PAGE, 1, "cuda:0", 1, 1)
     tag = {"config": args.tag, "window_GiB": args.window_gib, "prt": capi.get_option(capi.OPT_PRT),
-           "max_extent_pages": capi.get_option(119), "kfd_flush": capi.get_option(118)}
+           "max_extent_pages": capi.get_option(capi.OPT_MAX_EXTENT_PAGES), "kfd_flush": capi.get_option(capi.OPT_KFD_TLB_FLUSH_ACTIVE)}
 
     def flushes(phase, off, reps=30, busy=False):
         capi.flush_unmaps()

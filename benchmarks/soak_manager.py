@@ -75,8 +75,8 @@ def main():
     dev = "cuda:0"
     torch.cuda.set_device(0)
     vmm_ops.init_kvcached(dev, PAGE, False)
-    backend = {0: "hip", 2: "hybrid", 3: "drm"}[capi.get_option(108)]
-    max_extent_pages = int(capi.get_option(119)) if backend == "drm" and capi.get_option(110) else 1
+    backend = {0: "hip", 2: "hybrid", 3: "drm"}[capi.get_option(capi.OPT_EFFECTIVE_BACKEND)]
+    max_extent_pages = int(capi.get_option(capi.OPT_MAX_EXTENT_PAGES)) if backend == "drm" and capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) else 1
     capi_prt = 0
     blocks_per_page = PAGE // BLOCK_BYTES
     num_blocks = args.page_ids * blocks_per_page
@@ -86,8 +86,8 @@ def main():
     v_off = per_layer // 2 // 8
     m = kcm.KVCacheManager(num_blocks=num_blocks, block_size=BLOCK_TOKENS, cell_size=CELL, num_layers=LAYERS)
     assert m._post_init_done.wait(30)
-    capi_prt = capi.get_option(128)
-    lanes = capi.get_option(129)
+    capi_prt = capi.get_option(capi.OPT_PRT)
+    lanes = capi.get_option(capi.OPT_LANES_PER_BUFFER)
     ipc = m.page_allocator._ipc_name()
     full_limit = per_layer * LAYERS
     rng = np.random.default_rng(args.seed)
@@ -153,7 +153,7 @@ def main():
     n_ops = 0
     touched_sum = 0
     if args.touch_unbacked:
-        assert capi.get_option(128) or args.compat, "unbacked VA would fault"
+        assert capi.get_option(capi.OPT_PRT) or args.compat, "unbacked VA would fault"
     t_progress = time.time()
     while time.time() < t_end and not bad:
         n_ops += 1

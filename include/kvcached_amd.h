@@ -74,7 +74,7 @@ int kvc_unmap_from_kv_tensors(const int64_t *offsets, size_t n, int64_t group_id
  *   KVC_OPT_ZERO_BACKFILL  1 (default, "compat", as the reference does: csrc/ftensor.cpp:160-176) = unbacked VA reads as
  *                              zeros from the moment an unmap returns: with the drm backend on gfx950 it is a PRT
  *                              mapping (reads 0, writes dropped, no fault, no zero page: DESIGN.md §4.2;
- *                              kvc_get_option(128)), elsewhere or with KVCACHED_PRT=false it aliases zero pages (one
+ *                              kvc_get_option(KVC_OPT_PRT)), elsewhere or with KVCACHED_PRT=false it aliases zero pages (one
  *                              zero extent on drm, sharded pages through ROCr otherwise); map and unmap calls both
  *                              invalidate the GPU TLBs before they return (a PRT entry or a zero alias that something
  *                              has looked at is cached). 0 ("lazy", KVCACHED_ZERO_BACKFILL=false) = unbacked VA is
@@ -93,7 +93,7 @@ int kvc_unmap_from_kv_tensors(const int64_t *offsets, size_t n, int64_t group_id
  *                              (DESIGN.md §4.3); 0 only for measurements. The invalidation an unmap batch owes is
  *                              performed at once by a thread of the library (KVCACHED_ASYNC_SHOOTDOWN, default true;
  *                              compat mode and imported pages invalidate inside the call); kvc_flush_unmaps()
- *                              returns when nothing is owed or in flight; kvc_get_option(111) counts the
+ *                              returns when nothing is owed or in flight; kvc_get_option(KVC_OPT_BACKGROUND_SHOOTDOWNS) counts the
  *                              invalidations done off the callers' threads.
  *   KVC_OPT_DEFER_UNMAP_SHOOTDOWN 1 = the invalidation owed by an unmap batch whose pages all go back
  *                              to the library's own handle pool waits for the next map batch (which invalidates
@@ -105,17 +105,17 @@ int kvc_unmap_from_kv_tensors(const int64_t *offsets, size_t n, int64_t group_id
  *                              registers each slot with HIP once and then maps/unmaps it through ROCr's
  *                              hsa_amd_vmem_* (hipMemUnmap spins ~10 us on a GPU marker per mapping; ROCr's unmap
  *                              takes 3 us) - every hipMemcpy flavour keeps working; checked by a self test at
- *                              kvc_init, which falls back to hip. kvc_get_option(108) reports the backend in
+ *                              kvc_init, which falls back to hip. kvc_get_option(KVC_OPT_EFFECTIVE_BACKEND) reports the backend in
  *                              effect (0 hip, 1 hsa, 2 hybrid, 3 drm). drm = hybrid, and this process's own
  *                              pages are mapped/unmapped with one DRM_AMDGPU_GEM_VA ioctl each through
  *                              libdrm_amdgpu on buffer objects imported once per handle (2.2 + 2.1 us per page
  *                              instead of 5.3 + 2.8); self-tested at kvc_init, falls back to hybrid. With drm, physical
  *                              pages are also allocated straight from KFD (AMDKFD_IOC_ALLOC_MEMORY_OF_GPU on the
  *                              library's own fd of /dev/kfd: 5 us flat instead of the runtime's O(live handles);
- *                              KVCACHED_DRM_KFD_CREATE=false keeps ROCr's creation; kvc_get_option(110) = 1 when active).
+ *                              KVCACHED_DRM_KFD_CREATE=false keeps ROCr's creation; kvc_get_option(KVC_OPT_KFD_CREATE_ACTIVE) = 1 when active).
  *                              KVCACHED_PHYS_CHUNK_PAGES=k (default 1024, at most 1024; 1 = single pages) backs a run
  *                              of up to k adjacent slots with one buffer of that many pages and maps it with one ioctl
- *                              (run-sized extents; kvc_get_option(119) reports k).
+ *                              (run-sized extents; kvc_get_option(KVC_OPT_MAX_EXTENT_PAGES) reports k).
  *                              DESIGN.md §4.6/§4.7.
  *   KVC_OPT_UNMAP_INVALIDATION_US  compat regions only (env KVCACHED_UNMAP_INVALIDATION_US). 0 (default): kvc_unmap_from_kv_tensors
  *                          invalidates the GPU TLBs before it returns - a freed address reads as zeros from that moment on.
@@ -133,15 +133,67 @@ int kvc_unmap_from_kv_tensors(const int64_t *offsets, size_t n, int64_t group_id
  *                              ~15 us per slot to a queue push; queued bytes count as free in kvc_mem_get_info.
  *                              kvc_flush_unmaps() waits for the queue (trim/resize/shutdown do it themselves).
  *                              0 (default) = synchronous, like the reference. Ignored in compat mode.
- * Read-only diagnostics through kvc_get_option (numbers >= 100; kvcached_amd/capi.py names them): 108 backend in effect,
- * 110 pages straight from KFD, 111 invalidations done off the callers' threads, 112-117 page creation / release time
- * split, 118 the KFD ioctl pair is the invalidation in use, 119 pages per extent at most, 120-124 the extent pool's
- * footprint, 125/126 pages zeroed on their way back / handed out without a fill of their own, 127 pages of the zero
- * extent, 128 PRT behind unbacked VA, 129 lanes per buffer (page ids backed as units), 130-153 host nanoseconds of the map /
- * unmap calls by segment and ioctl counts (bench.py), 163/164 peer pages imported straight into KFD + DRM / through the runtime. */
+ * Every option number the library answers is named in the enum below (kvcached_amd/capi.py lists the same names as OPT_*;
+ * default, bounds and the KVCACHED_* variable behind each stored one: the table in kvcached_amd/csrc/options.cpp and
+ * INTEGRATION.md §5). Numbers >= 100 are tuning knobs and read-only diagnostics. */
 enum { KVC_OPT_ZERO_BACKFILL = 1, KVC_OPT_ZERO_FILL = 2, KVC_OPT_POOL_BYTES = 3, KVC_OPT_PROFILE = 4,
        KVC_OPT_TLB_SHOOTDOWN = 5, KVC_OPT_DEFER_UNMAP_SHOOTDOWN = 6, KVC_OPT_ASYNC_UNMAP = 7,
-       KVC_OPT_UNMAP_INVALIDATION_US = 8 };
+       KVC_OPT_UNMAP_INVALIDATION_US = 8,
+       /* tuning only */
+       KVC_OPT_FILL_VARIANT = 100, KVC_OPT_COMPACT_VARIANT = 101,
+       KVC_OPT_ACCESS_RUN_SLOTS = 102,    /* mappings one hipMemSetAccess call may span at most */
+       KVC_OPT_ZERO_ALIAS_FANOUT = 103,   /* unbacked slots per physical zero page; takes effect at the next create_kv_tensors */
+       KVC_OPT_FAIL_AFTER_CREATES = 104,  /* fault injection (tests): the (value+1)-th creation of physical memory fails; -1 = off */
+       KVC_OPT_FILL_CHUNK_SLOTS = 105,    /* slots made usable (one invalidation + fill launches) at a time */
+       KVC_OPT_POOL_IDLE_MS = 107,        /* idle pooled memory older than this goes back to the driver (0 = keep until pressure) */
+       KVC_OPT_ASYNC_SHOOTDOWN = 109,     /* unmap leaves its invalidation to a thread of the library */
+       /* read-only diagnostics */
+       KVC_OPT_EFFECTIVE_BACKEND = 108,   /* the VMM backend after init's self tests: 0 hip, 2 hybrid, 3 drm */
+       KVC_OPT_KFD_CREATE_ACTIVE = 110,   /* physical pages come straight from KFD */
+       KVC_OPT_BACKGROUND_SHOOTDOWNS = 111, /* invalidations done off the callers' threads */
+       KVC_OPT_KFD_ALLOC_NS = 112, KVC_OPT_KFD_EXPORT_NS = 113, KVC_OPT_DRM_IMPORT_NS = 114, /* page creation: time split ... */
+       KVC_OPT_KFD_CREATES = 115,                                                           /* ... and count */
+       KVC_OPT_KFD_FREE_NS = 116, KVC_OPT_KFD_FREES = 117,                                  /* DRM + KFD frees: time, count */
+       KVC_OPT_KFD_TLB_FLUSH_ACTIVE = 118, /* the direct KFD flush is the invalidation in use */
+       KVC_OPT_MAX_EXTENT_PAGES = 119,     /* pages per extent at most (KVCACHED_PHYS_CHUNK_PAGES at init) */
+       /* footprint of the pool the engine's pages come from, in pages: held from the driver, handed out, free inside partly
+        * used buffers (the waste), the size new buffers get right now; releases of pieces the pool did not know (stays 0) */
+       KVC_OPT_POOL_HELD_PAGES = 120, KVC_OPT_POOL_OUT_PAGES = 121, KVC_OPT_POOL_FREE_PIECES = 122,
+       KVC_OPT_POOL_EXTENT_PAGES_NOW = 123, KVC_OPT_POOL_BAD_RELEASES = 124,
+       KVC_OPT_PAGES_SCRUBBED = 125,      /* pages zeroed on their way back (reset with the stats) */
+       KVC_OPT_PAGES_PRESCRUBBED = 126,   /* pages a map call handed out without launching a fill for them */
+       KVC_OPT_ZERO_EXTENT_PAGES = 127,   /* pages of the zero extent behind compat-mode regions (0: PRT, or sharded zero pages) */
+       KVC_OPT_PRT = 128,                 /* unbacked slots of group 0 are PRT mappings: reads 0, writes dropped, no fault */
+       KVC_OPT_LANES_PER_BUFFER = 129,    /* page ids of group 0 are backed as units (lanes), this many to a buffer at most (0: no) */
+       /* 130 + i: host nanoseconds of the map / unmap calls by segment since the last reset, and three counts */
+       KVC_OPT_HOST_SEGMENT_0 = 130,
+       KVC_OPT_SEG_MAP_OFFSETS = 130,        /* map: offsets -> slots */
+       KVC_OPT_SEG_MAP_CLASSIFY = 131,
+       KVC_OPT_SEG_MAP_RUNS = 132,           /* sort into runs */
+       KVC_OPT_SEG_MAP_POOL = 133,
+       KVC_OPT_SEG_MAP_IOCTLS = 134,         /* page-table ioctls */
+       KVC_OPT_SEG_MAP_BOOKKEEPING = 135,    /* per run */
+       KVC_OPT_SEG_MAP_INVALIDATION = 136,   /* invalidation owed */
+       KVC_OPT_SEG_MAP_WAIT_FILL = 137,      /* wait for own fill */
+       KVC_OPT_SEG_MAP_WAIT_SCRUB = 138,     /* wait for the scrub of these pages */
+       KVC_OPT_SEG_MAP_SCRUBS_BEHIND = 139,  /* a count: scrubs behind the newest */
+       KVC_OPT_SEG_UNMAP_OFFSETS = 140,      /* unmap: offsets -> slots */
+       KVC_OPT_SEG_UNMAP_RUNS = 141,
+       KVC_OPT_SEG_UNMAP_IOCTLS = 142,
+       KVC_OPT_SEG_UNMAP_BOOKKEEPING = 143,  /* per slot */
+       KVC_OPT_SEG_UNMAP_REMAINDERS = 144,
+       KVC_OPT_SEG_UNMAP_EPOCHS = 145,
+       KVC_OPT_SEG_UNMAP_INVALIDATION = 146,
+       KVC_OPT_SEG_UNMAP_SCRUB_LAUNCH = 147,
+       KVC_OPT_SEG_UNMAP_POOL = 148,
+       KVC_OPT_SEG_KFD_REMAP_HALF = 149,     /* both: the re-MAP half of the KFD flush pairs */
+       KVC_OPT_SEG_MAP_REMAINDER_REWRITE = 150, /* map: rewrite of split PRT / zero-extent remainders (a share of 136) */
+       KVC_OPT_SEG_MAP_IOCTL_COUNT = 151,    /* a count: page-table ioctls issued by map calls */
+       KVC_OPT_SEG_UNMAP_IOCTL_COUNT = 152,  /* a count: ... by unmap calls */
+       KVC_OPT_SEG_MAP_RUN_COUNT = 153,      /* a count: runs of adjacent slots found by map calls */
+       KVC_OPT_SEG_END = 162,                /* 154..161 are reserved for further segments and read 0 */
+       /* shared pool: pages of a peer imported straight into KFD + DRM / through the runtime's import (ROCr, HIP) */
+       KVC_OPT_IMPORTS_DIRECT = 163, KVC_OPT_IMPORTS_RUNTIME = 164 };
 int kvc_set_option(int opt, int64_t value);
 int64_t kvc_get_option(int opt);
 int kvc_flush_unmaps(void); /* wait until every queued (async) unmap has been carried out */
@@ -344,7 +396,7 @@ int64_t kvc_unique_block_ids(const int64_t *token_indices_dev, size_t n, int64_t
  * the fds (received over SCM_RIGHTS) and map them at the same offsets. */
 int kvc_export_mapped_slots(const int64_t *offsets, size_t n, int64_t group_id, int *out_fds, int64_t cap); /* returns fd count */
 int kvc_map_imported_slots(const int64_t *offsets, size_t n, int64_t group_id, const int *fds, size_t n_fds);
-/* The same with page ids as units (multi-row geometries whose page ids are backed by lanes: kvc_get_option(129) > 0). ONE dmabuf fd
+/* The same with page ids as units (multi-row geometries whose page ids are backed by lanes: kvc_get_option(KVC_OPT_LANES_PER_BUFFER) > 0). ONE dmabuf fd
  * per BUFFER - up to 8 page ids live in one, their lanes side by side - instead of one per 2 MiB slot (64 per page id for
  * Llama-3-8B), and three numbers per page id that tell the peer where its pages are: meta[3i] = which of the exported fds,
  * meta[3i+1] = lanes that buffer holds (k), meta[3i+2] = the lane that is page id i's (j); the page behind row r is at byte

@@ -31,9 +31,9 @@ ARCH = "gfx950"
 
 # (tools_sanitize_cpu.sh builds the same list: `python kvcached_amd/build.py --print-lib-srcs`)
 LIB_SRCS = ["c_api.cpp", "kv_allocator.cpp", "kv_selftest.cpp", "kv_regions.cpp", "kv_map_paths.cpp", "kv_lanes.cpp", "kv_share.cpp", "gpu_context.cpp",
-            "page_allocator.cpp", "kernels.hip", "index_kernels.hip"]
+            "options.cpp", "page_allocator.cpp", "kernels.hip", "index_kernels.hip"]
 LIB_DEPS = LIB_SRCS + ["codec_math.hpp", "common.hpp", "hip_vmm.hpp", "drm_vm.hpp", "extent_pool.hpp", "gpu_context.hpp", "kernels.hpp", "kv_allocator.hpp",
-                       "kv_allocator_impl.hpp", "mem_info.hpp", "page_allocator.hpp", "run_scan.hpp", "../../include/kvcached_amd.h"]
+                       "kv_allocator_impl.hpp", "mem_info.hpp", "options.hpp", "page_allocator.hpp", "run_scan.hpp", "../../include/kvcached_amd.h"]
 EXT_SRCS = ["vmm_ops.cpp"]
 
 

@@ -24,24 +24,25 @@ lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
 
 KVC_OK, KVC_E_INVALID, KVC_E_GPU, KVC_E_NO_PAGES, KVC_E_RUNTIME, KVC_E_NO_GPU, KVC_E_CALLBACK = 0, -1, -2, -3, -4, -5, -6
 KVC_E_NOT_CREATED = -7
-OPT_ZERO_BACKFILL, OPT_ZERO_FILL, OPT_POOL_BYTES, OPT_PROFILE, OPT_TLB_SHOOTDOWN, OPT_DEFER_UNMAP_SHOOTDOWN = 1, 2, 3, 4, 5, 6
-OPT_ASYNC_UNMAP = 7
-OPT_UNMAP_INVALIDATION_US = 8   # compat: the invalidation an unmap owes may trail the call by this many microseconds (0: inside the call)
-OPT_FILL_VARIANT, OPT_COMPACT_VARIANT = 100, 101  # tuning only
-# read-only: the VMM backend in effect after init's self tests (0 hip, 2 hybrid, 3 drm), and whether physical
-# pages come straight from KFD (drm backend only)
-OPT_EFFECTIVE_BACKEND, OPT_KFD_CREATE_ACTIVE = 108, 110
-OPT_BACKGROUND_SHOOTDOWNS = 111  # read-only: TLB invalidations performed by the library's own threads so far
-# read-only: 112-117 KFD allocation / dmabuf export / DRM import ns, creations, free ns, frees; 118 the direct KFD TLB flush
-# is in use; 119 pages per physical extent at most; 120-123 pool footprint: pages held from the driver, pages handed out,
-# free pieces inside partly used extents (the waste), the extent size new runs get right now
-OPT_KFD_TLB_FLUSH_ACTIVE, OPT_MAX_EXTENT_PAGES = 118, 119
-OPT_POOL_HELD_PAGES, OPT_POOL_OUT_PAGES, OPT_POOL_FREE_PIECES, OPT_POOL_EXTENT_PAGES_NOW = 120, 121, 122, 123
-# read-only: pages zeroed on their way back to the pool / handed out by map calls that had nothing left to zero (§4.9)
-OPT_PAGES_SCRUBBED, OPT_PAGES_PRESCRUBBED = 125, 126
-OPT_ZERO_EXTENT_PAGES = 127  # read-only: compat mode aliases a zero extent of this many pages (0: PRT, or sharded zero pages through ROCr)
-OPT_PRT = 128                # read-only: unbacked slots are PRT mappings (reads 0, writes dropped, no fault): the compat default on drm/gfx950
-OPT_HOST_SEGMENT_0 = 130     # read-only, 130..149: host ns of the map/unmap calls by segment since the last reset (bench.py HOST_SEGMENTS)
+# Every option number of kvc_set_option / kvc_get_option, under the names of the enum in include/kvcached_amd.h (what each is:
+# the comments there; tests/test_options.py holds the two lists to each other).
+OPT_ZERO_BACKFILL, OPT_ZERO_FILL, OPT_POOL_BYTES, OPT_PROFILE, OPT_TLB_SHOOTDOWN = 1, 2, 3, 4, 5
+OPT_DEFER_UNMAP_SHOOTDOWN, OPT_ASYNC_UNMAP, OPT_UNMAP_INVALIDATION_US, OPT_FILL_VARIANT = 6, 7, 8, 100
+OPT_COMPACT_VARIANT, OPT_ACCESS_RUN_SLOTS, OPT_ZERO_ALIAS_FANOUT, OPT_FAIL_AFTER_CREATES = 101, 102, 103, 104
+OPT_FILL_CHUNK_SLOTS, OPT_POOL_IDLE_MS, OPT_ASYNC_SHOOTDOWN, OPT_EFFECTIVE_BACKEND = 105, 107, 109, 108
+OPT_KFD_CREATE_ACTIVE, OPT_BACKGROUND_SHOOTDOWNS, OPT_KFD_ALLOC_NS, OPT_KFD_EXPORT_NS = 110, 111, 112, 113
+OPT_DRM_IMPORT_NS, OPT_KFD_CREATES, OPT_KFD_FREE_NS, OPT_KFD_FREES, OPT_KFD_TLB_FLUSH_ACTIVE = 114, 115, 116, 117, 118
+OPT_MAX_EXTENT_PAGES, OPT_POOL_HELD_PAGES, OPT_POOL_OUT_PAGES, OPT_POOL_FREE_PIECES = 119, 120, 121, 122
+OPT_POOL_EXTENT_PAGES_NOW, OPT_POOL_BAD_RELEASES, OPT_PAGES_SCRUBBED, OPT_PAGES_PRESCRUBBED = 123, 124, 125, 126
+OPT_ZERO_EXTENT_PAGES, OPT_PRT, OPT_LANES_PER_BUFFER, OPT_HOST_SEGMENT_0, OPT_SEG_MAP_OFFSETS = 127, 128, 129, 130, 130
+OPT_SEG_MAP_CLASSIFY, OPT_SEG_MAP_RUNS, OPT_SEG_MAP_POOL, OPT_SEG_MAP_IOCTLS = 131, 132, 133, 134
+OPT_SEG_MAP_BOOKKEEPING, OPT_SEG_MAP_INVALIDATION, OPT_SEG_MAP_WAIT_FILL = 135, 136, 137
+OPT_SEG_MAP_WAIT_SCRUB, OPT_SEG_MAP_SCRUBS_BEHIND, OPT_SEG_UNMAP_OFFSETS, OPT_SEG_UNMAP_RUNS = 138, 139, 140, 141
+OPT_SEG_UNMAP_IOCTLS, OPT_SEG_UNMAP_BOOKKEEPING, OPT_SEG_UNMAP_REMAINDERS = 142, 143, 144
+OPT_SEG_UNMAP_EPOCHS, OPT_SEG_UNMAP_INVALIDATION, OPT_SEG_UNMAP_SCRUB_LAUNCH = 145, 146, 147
+OPT_SEG_UNMAP_POOL, OPT_SEG_KFD_REMAP_HALF, OPT_SEG_MAP_REMAINDER_REWRITE = 148, 149, 150
+OPT_SEG_MAP_IOCTL_COUNT, OPT_SEG_UNMAP_IOCTL_COUNT, OPT_SEG_MAP_RUN_COUNT, OPT_SEG_END = 151, 152, 153, 162
+OPT_IMPORTS_DIRECT, OPT_IMPORTS_RUNTIME = 163, 164
 
 _vp, _i64, _int, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t
 _I64P = ctypes.POINTER(ctypes.c_int64)

@@ -112,116 +112,62 @@ int kvc_unmap_from_kv_tensors(const int64_t *offsets, size_t n, int64_t group_id
   });
 }
 
+// The stored options are rows of the table in options.cpp; the names of all numbers: include/kvcached_amd.h.
 int kvc_set_option(int opt, int64_t value) {
-  switch (opt) {
-  case KVC_OPT_ZERO_BACKFILL: options().zero_backfill = value; break;
-  case KVC_OPT_ZERO_FILL: options().zero_fill = value; break;
-  case KVC_OPT_POOL_BYTES: options().pool_bytes = value; break;
-  case KVC_OPT_PROFILE: options().profile = value; break;
-  case KVC_OPT_TLB_SHOOTDOWN: options().tlb_shootdown = value; break;
-  case KVC_OPT_DEFER_UNMAP_SHOOTDOWN: options().defer_unmap_shootdown = value; break;
-  case KVC_OPT_ASYNC_UNMAP:
-    if (!value) KvAllocator::flush_all_unmaps(); // switching off: nothing may stay queued
-    options().async_unmap = value;
-    break;
-  case KVC_OPT_UNMAP_INVALIDATION_US:
-    if (value <= 0) { // switching off: nothing may stay parked behind an invalidation nobody is in a hurry for
-      if (GpuContext *ctx = KvAllocator::gpu()) ctx->flush_limbo();
-    }
-    options().deferred_unmap_flush_us = value < 0 ? 0 : value;
-    break;
-  case 102: options().access_run_slots = value; break; // tuning only
-  case 103: options().zero_alias_fanout = value; break; // takes effect at the next create_kv_tensors
-  case 105: options().fill_chunk_slots = value < 1 ? 1 : value; break; // tuning only
-  case 107: options().pool_idle_ms = value < 0 ? 0 : value; break;
-  case 109: options().async_shootdown = value; break;
-  case 104: fail_after_creates() = value; break;       // fault injection: the (value+1)-th hipMemCreate fails
-  case 100: options().fill_variant = value; break;    // tuning only
-  case 101: options().compact_variant = value; break; // tuning only
-  default: return fail(KVC_E_INVALID, "unknown option");
-  }
+  if (opt == KVC_OPT_ASYNC_UNMAP && !value) KvAllocator::flush_all_unmaps(); // switching off: nothing may stay queued
+  if (opt == KVC_OPT_UNMAP_INVALIDATION_US && value <= 0) // ... nor parked behind an invalidation nobody is in a hurry for
+    if (GpuContext *ctx = KvAllocator::gpu()) ctx->flush_limbo();
+  if (opt == KVC_OPT_FAIL_AFTER_CREATES) fail_after_creates() = value;
+  else if (!set_stored_option(opt, value)) return fail(KVC_E_INVALID, "unknown option");
   return KVC_OK;
 }
 int64_t kvc_get_option(int opt) {
+  int64_t stored;
+  if (get_stored_option(opt, &stored)) return stored;
+  if (opt >= KVC_OPT_HOST_SEGMENT_0 && opt < KVC_OPT_SEG_END) return stats().seg[opt - KVC_OPT_HOST_SEGMENT_0];
+  GpuContext *ctx = nullptr; // (computed diagnostics, all read-only)
   switch (opt) {
-  case KVC_OPT_ZERO_BACKFILL: return options().zero_backfill;
-  case KVC_OPT_ZERO_FILL: return options().zero_fill;
-  case KVC_OPT_POOL_BYTES: return options().pool_bytes;
-  case KVC_OPT_PROFILE: return options().profile;
-  case KVC_OPT_TLB_SHOOTDOWN: return options().tlb_shootdown;
-  case KVC_OPT_DEFER_UNMAP_SHOOTDOWN: return options().defer_unmap_shootdown;
-  case KVC_OPT_ASYNC_UNMAP: return options().async_unmap;
-  case KVC_OPT_UNMAP_INVALIDATION_US: return options().deferred_unmap_flush_us;
-  case 102: return options().access_run_slots;
-  case 103: return options().zero_alias_fanout;
-  case 105: return options().fill_chunk_slots;
-  case 107: return options().pool_idle_ms;
-  case 109: return options().async_shootdown;
-  case 108: return vmm_backend().load(); // effective VMM backend: 0 hip, 2 hybrid, 3 drm (read-only)
-  case 111: return background_shootdowns().load(); // TLB invalidations done by the library's own threads (read-only)
-  case 110: return vmm_backend().load() == kVmmDrm && DrmVm::instance().kfd_ready() ? 1 : 0; // physical pages straight from KFD (read-only)
-  case 112: return DrmVm::instance().create_times().alloc_ns.load();  // KFD allocation ioctls, ns (read-only, 112-117)
-  case 113: return DrmVm::instance().create_times().export_ns.load(); // dmabuf exports
-  case 114: return DrmVm::instance().create_times().import_ns.load(); // imports into DRM
-  case 115: return DrmVm::instance().create_times().count.load();
-  case 116: return DrmVm::instance().create_times().free_ns.load();   // DRM + KFD frees
-  case 117: return DrmVm::instance().create_times().frees.load();
-  // 130..149: host nanoseconds of the map / unmap calls by segment since the last reset (read-only diagnostics).
-  // map: 130 offsets -> slots, 131 classify, 132 sort into runs, 133 pool, 134 page-table ioctls, 135 per-run bookkeeping,
-  // 136 invalidation owed, 137 wait for own fill, 138 wait for the scrub of these pages, 139 (a count: scrubs behind the newest); unmap: 140 offsets -> slots, 141 runs, 142 page-table ioctls, 143 per-slot bookkeeping,
-  // 144 remainders, 145 epochs, 146 invalidation, 147 scrub launch, 148 pool
-  case 130: case 131: case 132: case 133: case 134: case 135: case 136: case 137: case 138: case 139:
-  case 140: case 141: case 142: case 143: case 144: case 145: case 146: case 147: case 148: case 149:
-    return stats().seg[opt - 130];
-  // 150..161: more of the same. 150 map: rewrite of split PRT / zero-extent remainders (a share of 136), 151 map: page-table
-  // ioctls issued (a count), 152 unmap: page-table ioctls issued (a count), 153 map: runs of adjacent slots (a count)
-  case 150: case 151: case 152: case 153: case 154: case 155: case 156: case 157: case 158: case 159: case 160: case 161:
-    return stats().seg[opt - 130];
-  case 118: { // the direct KFD TLB flush is what tlb_shootdown() uses (read-only)
-    GpuContext *ctx = KvAllocator::gpu();
-    return ctx && ctx->kfd_flush_active() ? 1 : 0;
-  }
-  case 119: return options().phys_chunk_pages; // pages per extent at most (read-only; KVCACHED_PHYS_CHUNK_PAGES at init)
-  case 120: case 121: case 122: case 123: { // footprint of the pool the engine's pages come from, in pages: held from the driver,
-    // handed out, free inside partly used buffers (the waste), and the size new buffers get right now (read-only)
-    GpuContext *ctx = KvAllocator::gpu();
-    if (!ctx) return 0;
+  case KVC_OPT_FAIL_AFTER_CREATES: return fail_after_creates();
+  case KVC_OPT_EFFECTIVE_BACKEND: return vmm_backend().load();
+  case KVC_OPT_BACKGROUND_SHOOTDOWNS: return background_shootdowns().load();
+  case KVC_OPT_KFD_CREATE_ACTIVE: return vmm_backend().load() == kVmmDrm && DrmVm::instance().kfd_ready() ? 1 : 0;
+  case KVC_OPT_KFD_ALLOC_NS: return DrmVm::instance().create_times().alloc_ns.load();
+  case KVC_OPT_KFD_EXPORT_NS: return DrmVm::instance().create_times().export_ns.load();
+  case KVC_OPT_DRM_IMPORT_NS: return DrmVm::instance().create_times().import_ns.load();
+  case KVC_OPT_KFD_CREATES: return DrmVm::instance().create_times().count.load();
+  case KVC_OPT_KFD_FREE_NS: return DrmVm::instance().create_times().free_ns.load();
+  case KVC_OPT_KFD_FREES: return DrmVm::instance().create_times().frees.load();
+  case KVC_OPT_KFD_TLB_FLUSH_ACTIVE: return (ctx = KvAllocator::gpu()) && ctx->kfd_flush_active() ? 1 : 0;
+  case KVC_OPT_POOL_HELD_PAGES: case KVC_OPT_POOL_OUT_PAGES: case KVC_OPT_POOL_FREE_PIECES: case KVC_OPT_POOL_EXTENT_PAGES_NOW: {
+    if (!(ctx = KvAllocator::gpu())) return 0;
     ExtentPool *p = ctx->primary_pool();
-    if (!p) return opt == 123 ? (int64_t)options().phys_chunk_pages.load() : 0; // (nothing mapped yet: no pool is made for a diagnostic)
+    // (nothing mapped yet: no pool is made for a diagnostic)
+    if (!p) return opt == KVC_OPT_POOL_EXTENT_PAGES_NOW ? (int64_t)options().phys_chunk_pages.load() : 0;
     const auto f = p->footprint();
     const int64_t scale = (int64_t)p->counter_scale();
-    return scale * (int64_t)(opt == 120 ? f.held_pages : opt == 121 ? f.out_pages : opt == 122 ? f.free_pieces : f.extent_pages_now);
+    return scale * (int64_t)(opt == KVC_OPT_POOL_HELD_PAGES    ? f.held_pages
+                             : opt == KVC_OPT_POOL_OUT_PAGES   ? f.out_pages
+                             : opt == KVC_OPT_POOL_FREE_PIECES ? f.free_pieces
+                                                               : f.extent_pages_now);
   }
-  case 127: { // pages of the zero extent behind compat-mode regions (0: none - PRT, or sharded zero pages through ROCr; read-only)
-    GpuContext *ctx = KvAllocator::gpu();
-    return ctx ? (int64_t)ctx->zero_extent_pages(KvAllocator::page_size()) : 0;
-  }
-  case 128: { // unbacked slots of group 0 are PRT mappings: reads return 0, writes are dropped, nothing faults (read-only)
-    try {
-      return KvAllocator::initialized() && KvAllocator::global(0)->uses_prt() ? 1 : 0;
-    } catch (...) {
-      return 0;
-    }
-  }
-  case 125: return stats().pages_scrubbed;    // pages zeroed on their way back (read-only; reset with the stats)
-  case 126: return stats().pages_prescrubbed; // pages a map call handed out without launching a fill for them
-  case 124: { // releases of pieces the pool did not know (must stay 0; read-only)
-    GpuContext *ctx = KvAllocator::gpu();
-    ExtentPool *p = ctx ? ctx->primary_pool() : nullptr;
+  case KVC_OPT_POOL_BAD_RELEASES: {
+    ExtentPool *p = (ctx = KvAllocator::gpu()) ? ctx->primary_pool() : nullptr;
     return p ? (int64_t)p->footprint().bad_releases : 0;
   }
-  case 163: return import_count(true);  // shared pool: pages of a peer imported straight into KFD + DRM (read-only)
-  case 164: return import_count(false); // ... and through the runtime's import (ROCr / HIP): the fallback, e.g. for a buffer on another GPU
-  case 129: { // page ids of group 0 are backed as units (lanes: DESIGN.md §4.11), and how many lanes a buffer holds at most (0: no; read-only)
+  case KVC_OPT_PAGES_SCRUBBED: return stats().pages_scrubbed;
+  case KVC_OPT_PAGES_PRESCRUBBED: return stats().pages_prescrubbed;
+  case KVC_OPT_ZERO_EXTENT_PAGES: return (ctx = KvAllocator::gpu()) ? (int64_t)ctx->zero_extent_pages(KvAllocator::page_size()) : 0;
+  case KVC_OPT_PRT:
+  case KVC_OPT_LANES_PER_BUFFER:
     try {
-      return KvAllocator::initialized() ? (int64_t)KvAllocator::global(0)->lanes_per_extent() : 0;
+      if (!KvAllocator::initialized()) return 0;
+      KvAllocator *a = KvAllocator::global(0);
+      return opt == KVC_OPT_PRT ? (a->uses_prt() ? 1 : 0) : (int64_t)a->lanes_per_extent();
     } catch (...) {
       return 0;
     }
-  }
-  case 104: return fail_after_creates();
-  case 100: return options().fill_variant;
-  case 101: return options().compact_variant;
+  case KVC_OPT_IMPORTS_DIRECT: return import_count(true);
+  case KVC_OPT_IMPORTS_RUNTIME: return import_count(false);
   default: return fail(KVC_E_INVALID, "unknown option");
   }
 }

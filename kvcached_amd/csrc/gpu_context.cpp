@@ -11,10 +11,6 @@
 namespace kvc {
 
 // ------------------------------------------------------------------ globals
-Options &options() {
-  static Options o;
-  return o;
-}
 Stats &stats() {
   static Stats s;
   return s;
@@ -58,7 +54,7 @@ GpuContext::GpuContext(int dev) : dev_(dev) {
                        std::to_string(gran));
   HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   HIP_CHECK(hipStreamCreateWithFlags(&scrub_stream_, hipStreamNonBlocking));
-  if (env_bool("KVCACHED_KFD_TLB_FLUSH", true)) {
+  if (env_option("KVCACHED_KFD_TLB_FLUSH")) {
     std::string why;
     if (!kfd_flush_.open(dev_, &why))
       KVC_LOG(LOG_WARNING, "direct KFD TLB flush unavailable (%s): invalidating through hipMalloc + hipFree", why.c_str());
@@ -119,11 +115,7 @@ bool device_under_pressure() {
     (void)hipGetLastError();
     return false;
   }
-  static const double util = []() {
-    const char *e = std::getenv("KVCACHED_GPU_UTILIZATION");
-    return e ? std::atof(e) : 0.95;
-  }();
-  return free_b < static_cast<size_t>(total_b * (1.0 - util));
+  return free_b < static_cast<size_t>(total_b * (1.0 - env_gpu_utilization()));
 }
 } // namespace
 
@@ -224,8 +216,8 @@ ExtentPool *GpuContext::lane_extents(size_t rows, size_t page_bytes) {
   // PageAllocator keeps up to 10 freed ids mapped for reuse - pins the other lanes of its buffer: 8 lanes keep that to
   // 7 lanes per straggler (64-lane buffers of a small geometry pinned 1 GiB each in tests/test_gpu_colocation.py), and
   // beyond 8 the gain is small (the ioctl count per call is rows x ceil(ids / lanes): 64 for 8 page ids either way).
-  const size_t cap_b = (size_t)std::max<int64_t>(1, env_i64("KVCACHED_LANE_EXTENT_MB", 1024)) << 20;
-  const size_t want_k = (size_t)std::min<int64_t>(kMaxLanesPerBuffer, std::max<int64_t>(1, env_i64("KVCACHED_LANES_PER_BUFFER", 8)));
+  const size_t cap_b = (size_t)env_option("KVCACHED_LANE_EXTENT_MB");
+  const size_t want_k = (size_t)env_option("KVCACHED_LANES_PER_BUFFER");
   const unsigned k = (unsigned)std::min<size_t>(want_k, std::max<size_t>(1, cap_b / lane_bytes));
   std::unique_ptr<ExtentPool> old;
   ExtentPool *p;
@@ -318,7 +310,7 @@ void GpuContext::housekeeping() {
   // page ids mapped at all times.)
   if (primary) {
     const int64_t last = fg_last_ns_.load();
-    if (fg_active_.load() == 0 && last != 0 && now_ns() - last >= std::max<int64_t>(1, env_i64("KVCACHED_RESERVE_IDLE_S", 10)) * 1000000000ll) reserve_b = 0;
+    if (fg_active_.load() == 0 && last != 0 && now_ns() - last >= env_option("KVCACHED_RESERVE_IDLE_S") * 1000000000ll) reserve_b = 0;
   }
   // The reserve follows demand. What a map call has to CREATE it pays for on its caller's thread - 2 us per
   // buffer on VRAM the kernel has wiped, but ~50-80 us per 2 MiB on VRAM it has not handed out yet (cleared inside the
@@ -346,8 +338,8 @@ void GpuContext::housekeeping() {
     for (auto d : demand_window_) last_second += d;
     demand_quiet_ticks_ = delta ? 0 : demand_quiet_ticks_ + 1;
     const size_t max_units = std::min((size_t)std::max<int64_t>(0, options().pool_bytes.load()),
-                                      (size_t)std::max<int64_t>(0, env_i64("KVCACHED_PHYS_RESERVE_MAX_MB", 16384)) << 20) / primary->page_bytes();
-    if (env_bool("KVCACHED_ADAPTIVE_RESERVE", true) && reserve_b > 0) {
+                                      (size_t)env_option("KVCACHED_PHYS_RESERVE_MAX_MB")) / primary->page_bytes();
+    if (env_option("KVCACHED_ADAPTIVE_RESERVE") && reserve_b > 0) {
       reserve_boost_units_ = std::min(max_units, 2 * last_second); // (0 once a whole second has passed without a creation on anybody's path)
     } else {
       reserve_boost_units_ = 0;
@@ -868,7 +860,7 @@ void GpuContext::do_shootdown() {
     // answer it from a cache.
     int64_t map_ns = 0;
     if (!kfd_flush_.flush(&map_ns)) throw GpuError(std::string("KFD TLB flush failed: ") + strerror(errno));
-    stats().seg[19] += map_ns; // (diagnostics, option 149: the re-MAP half of the pair; the UNMAP half is the flush itself)
+    stats().seg[kSegKfdRemapHalf] += map_ns; // (diagnostics: the re-MAP half of the pair; the UNMAP half is the flush itself)
   } else {
     // Fallback where /dev/kfd cannot be driven directly: an allocation that reaches KFD. 2 MiB is the smallest size
     // ROCr does not serve from its sub-allocator (measured: 4 KiB has no effect). What invalidates is the FREE (KFD's

@@ -1,4 +1,4 @@
-// gpu_context.hpp — process-wide options and statistics, and the per-device state of the allocator (implemented in
+// gpu_context.hpp — process-wide statistics (the options: options.hpp), and the per-device state of the allocator (implemented in
 // gpu_context.cpp): streams, kernel launches, the physical pools, the alias arena and the scrub queue, the zero extent,
 // the TLB invalidation with its epochs.
 #pragma once
@@ -16,38 +16,11 @@
 
 #include "common.hpp"
 #include "hip_vmm.hpp"
+#include "options.hpp"
 
 namespace kvc {
 
-struct Options {
-  std::atomic<int64_t> zero_backfill{0};
-  std::atomic<int64_t> zero_fill{1};
-  std::atomic<int64_t> pool_bytes{16384ll << 20};
-  std::atomic<int64_t> profile{0};
-  std::atomic<int64_t> tlb_shootdown{1};
-  std::atomic<int64_t> pool_idle_ms{1000};       // idle handles older than this are released (0 = keep until pressure)
-  std::atomic<int64_t> async_unmap{0};           // unmap_from_kv_tensors only queues; a reclaimer thread does the driver calls
-  std::atomic<int64_t> async_shootdown{1};       // with a housekeeping thread around, unmap leaves its TLB invalidation to it
-  std::atomic<int64_t> hip_reg_group_mb{64};     // hybrid/drm: VA introduced to HIP per hipMemMap (0 = slot by slot)
-  std::atomic<int64_t> clear_run_slots{16};      // drm backend: unmap runs of adjacent slots with one CLEAR ioctl (0 = off)
-  std::atomic<int64_t> phys_chunk_pages{kMaxExtentPages}; // drm backend: a run of adjacent slots is backed by ONE buffer of up to this many pages (1 = off)
-  std::atomic<int64_t> extent_waste_pct{5};      // ... and new extents shrink while free pieces of partly used ones exceed this share of the pages in use
-  std::atomic<int64_t> phys_reserve_bytes{0};    // idle physical memory the housekeeping thread keeps ready (pre-created, never below it)
-  std::atomic<int64_t> map_waits_for_all_flushes{0}; // 1 = a map batch waits for every invalidation owed, not only those of its own slots
-  std::atomic<int64_t> scrub_on_release{1};      // drm backend: pages are zeroed (through an alias mapping) when they come back, not when they go out
-  std::atomic<int64_t> map_shootdown_always{0};  // 1 = invalidate after every map batch even when no stale translation can exist
-  std::atomic<int64_t> defer_unmap_shootdown{0}; // unmap's invalidation may wait for the next map batch / driver release
-  // compat regions: the invalidation an unmap owes may trail the call by at most `deferred_unmap_flush_us` (0 = inside the call,
-  // the default): the pages wait un-scrubbed and un-offered until it has happened, and the next map batch's own invalidation
-  // absorbs it if it comes first (KVCACHED_UNMAP_INVALIDATION_US)
-  std::atomic<int64_t> deferred_unmap_flush_us{0};
-  std::atomic<int64_t> access_run_slots{1}; // max mappings one hipMemSetAccess call may span
-  std::atomic<int64_t> zero_alias_fanout{256}; // unbacked slots that share one physical zero page
-  std::atomic<int64_t> fill_chunk_slots{1024}; // slots made usable (one TLB shootdown + fill launches) at a time
-  std::atomic<int64_t> fill_variant{0};
-  std::atomic<int64_t> compact_variant{0};
-};
-Options &options();
+static_assert(kMaxChunkPages == kMaxExtentPages, "the option table's bound is the extent pool's");
 
 struct Stats {
   std::atomic<int64_t> pages_mapped{0}, pages_unmapped{0};
@@ -60,8 +33,8 @@ struct Stats {
   std::atomic<int64_t> unmaps_queued{0}, unmaps_cancelled{0}; // async unmap: slots queued / re-backed before the reclaimer got to them
   // host time inside each driver call of the map/unmap paths (diagnostics; kvc_get_driver_breakdown)
   std::atomic<int64_t> t_unmap_alias{0}, t_acquire{0}, t_map{0}, t_access{0}, t_unmap{0}, t_release{0}, t_realias{0}, t_sync{0};
-  // host time of the map / unmap calls by segment (diagnostics, read-only options 130 + i; names in c_api.cpp)
-  std::atomic<int64_t> seg[32] = {};
+  // host time of the map / unmap calls by segment (diagnostics, read-only options KVC_OPT_HOST_SEGMENT_0 + i; enum Seg)
+  std::atomic<int64_t> seg[kSegCount] = {};
   std::mutex mu;
   double fill_ms = 0, compact_ms = 0;
   VmmCounters vmm;
@@ -70,7 +43,7 @@ struct Stats {
 Stats &stats();
 struct SegTimer { // accumulates the time since the previous mark into stats().seg[i]
   int64_t t = now_ns();
-  void mark(int i) {
+  void mark(Seg i) {
     const int64_t n = now_ns();
     stats().seg[i] += n - t;
     t = n;

@@ -42,6 +42,7 @@
 
 #include "common.hpp"
 #include "extent_pool.hpp"
+#include "options.hpp"
 
 namespace kvc {
 
@@ -56,7 +57,7 @@ inline void hip_check(hipError_t st, const char *tok, const char *file, int line
   snprintf(buf, sizeof buf, "%s:%d %s failed in HIP runtime (%u): %s", base ? base + 1 : file, line, tok,
            (unsigned)st, hipGetErrorString(st));
   (void)hipGetLastError(); // clear the sticky error
-  if (env_bool("KVCACHED_STRICT_ABORT", false)) {
+  if (env_option("KVCACHED_STRICT_ABORT")) {
     fprintf(stderr, "%s\n", buf);
     std::abort();
   }
@@ -100,7 +101,7 @@ inline void hsa_check(hsa_status_t st, const char *tok, const char *file, int li
   char buf[512];
   const char *base = strrchr(file, '/');
   snprintf(buf, sizeof buf, "%s:%d %s failed in ROCr (0x%x): %s", base ? base + 1 : file, line, tok, (unsigned)st, msg);
-  if (env_bool("KVCACHED_STRICT_ABORT", false)) {
+  if (env_option("KVCACHED_STRICT_ABORT")) {
     fprintf(stderr, "%s\n", buf);
     std::abort();
   }

@@ -76,36 +76,15 @@ void KvAllocator::init(const std::string &dev_str, size_t page_size, bool contig
                          ", must be a multiple of 2MB (2097152 bytes)");
     g_page_size = page_size;
   }
-  // environment knobs, read once per init
-  // Default ON since round 2, as in the reference (csrc/ftensor.cpp:160-176: unbacked VA reads as zeros instead of
-  // faulting). Round 1 had it off: with per-slot aliases through ROCr every creation cost O(mappings in the process) and
-  // the cycle ran at 160 GB/s; with the drm backend's zero extent (backfill_all) it is 1.5 TB/s and start-up is 2 304
-  // ioctls for a 288 GiB reservation. KVCACHED_ZERO_BACKFILL=false ("lazy": unbacked VA stays unmapped, a stray access
-  // FAULTS) is the opt-in for engines that never touch a block they do not own: 4.3 TB/s, no invalidation on the
-  // allocation path.
-  options().zero_backfill = env_bool("KVCACHED_ZERO_BACKFILL", true) ? 1 : 0;
-  options().zero_fill = env_bool("KVCACHED_ZERO_FILL", true) ? 1 : 0;
-  options().pool_bytes = env_i64("KVCACHED_PHYS_POOL_MB", 16384) << 20;
-  options().tlb_shootdown = env_bool("KVCACHED_TLB_SHOOTDOWN", true) ? 1 : 0;
-  options().defer_unmap_shootdown = env_bool("KVCACHED_DEFER_UNMAP_SHOOTDOWN", false) ? 1 : 0;
-  options().pool_idle_ms = std::max<int64_t>(0, env_i64("KVCACHED_POOL_IDLE_MS", 1000));
-  options().async_unmap = env_bool("KVCACHED_ASYNC_UNMAP", false) ? 1 : 0;
-  options().async_shootdown = env_bool("KVCACHED_ASYNC_SHOOTDOWN", true) ? 1 : 0;
-  options().hip_reg_group_mb = std::max<int64_t>(0, env_i64("KVCACHED_HIP_REG_GROUP_MB", 64));
-  options().clear_run_slots = std::max<int64_t>(0, env_i64("KVCACHED_DRM_CLEAR_RUN", 16));
-  options().phys_chunk_pages = std::min<int64_t>(kMaxExtentPages, std::max<int64_t>(1, env_i64("KVCACHED_PHYS_CHUNK_PAGES", kMaxExtentPages)));
-  options().extent_waste_pct = std::min<int64_t>(100, std::max<int64_t>(0, env_i64("KVCACHED_EXTENT_WASTE_PCT", 5)));
-  options().phys_reserve_bytes = std::max<int64_t>(0, env_i64("KVCACHED_PHYS_RESERVE_MB", 2048)) << 20;
-  options().scrub_on_release = env_bool("KVCACHED_SCRUB_ON_RELEASE", true) ? 1 : 0;
-  options().map_waits_for_all_flushes = env_bool("KVCACHED_MAP_WAITS_FOR_ALL_FLUSHES", false) ? 1 : 0;
-  options().deferred_unmap_flush_us = std::max<int64_t>(0, env_i64("KVCACHED_UNMAP_INVALIDATION_US", 0));
+  // environment knobs, read once per init: one row each in options.cpp.
+  // KVCACHED_ZERO_BACKFILL is ON by default since round 2, as in the reference (csrc/ftensor.cpp:160-176: unbacked VA reads as
+  // zeros instead of faulting). Round 1 had it off: with per-slot aliases through ROCr every creation cost O(mappings in the
+  // process) and the cycle ran at 160 GB/s; with the drm backend's zero extent (backfill_all) it is 1.5 TB/s and start-up is
+  // 2 304 ioctls for a 288 GiB reservation. =false ("lazy": unbacked VA stays unmapped, a stray access FAULTS) is the opt-in
+  // for engines that never touch a block they do not own: 4.3 TB/s, no invalidation on the allocation path.
+  load_options_from_env();
   {
-    const char *ms = std::getenv("KVCACHED_MAP_SHOOTDOWN");
-    options().map_shootdown_always = (ms && std::string(ms) == "always") ? 1 : 0;
-  }
-  {
-    const char *be = std::getenv("KVCACHED_VMM_BACKEND");
-    const std::string b = be ? be : "drm";
+    const std::string b = env_word("KVCACHED_VMM_BACKEND");
     if (b != "hip" && b != "hybrid" && b != "drm")
       throw InvalidError("KVCACHED_VMM_BACKEND must be 'drm', 'hybrid' or 'hip'");
     const int want = b == "hybrid" ? kVmmHybrid : (b == "drm" ? kVmmDrm : kVmmHip);
@@ -114,9 +93,6 @@ void KvAllocator::init(const std::string &dev_str, size_t page_size, bool contig
     for (auto &kv : g_contexts) kv.second->drain_pools();
     vmm_backend() = want;
   }
-  options().access_run_slots = std::max<int64_t>(1, env_i64("KVCACHED_ACCESS_RUN_SLOTS", 1));
-  options().zero_alias_fanout = std::max<int64_t>(1, env_i64("KVCACHED_ZERO_ALIAS_FANOUT", 256));
-  options().fill_chunk_slots = std::max<int64_t>(1, env_i64("KVCACHED_FILL_CHUNK_SLOTS", 1024));
   g_device = want_dev;
   g_contiguous = contiguous_layout;
   if (g_device.is_gpu) {
@@ -213,7 +189,7 @@ void device_synchronize() {
 // ------------------------------------------------------------------ KvAllocator
 KvAllocator::KvAllocator(DeviceSpec dev, bool contiguous_layout, GpuContext *ctx)
     : dev_(dev), contiguous_(contiguous_layout), ctx_(ctx) {
-  exportable_ = env_bool("KVCACHED_EXPORTABLE_HANDLES", false);
+  exportable_ = env_option("KVCACHED_EXPORTABLE_HANDLES") != 0;
 }
 
 KvAllocator::~KvAllocator() {
@@ -542,7 +518,7 @@ bool KvAllocator::map_to_kv_tensors(const offset_t *offsets, size_t n) {
     return true;
   }
   const auto slots = slots_for(offsets, n);
-  sg.mark(0);
+  sg.mark(kSegMapOffsets);
   map_slots(slots, nullptr);
   stats().map_calls++;
   stats().map_ns += now_ns() - t0;
@@ -572,7 +548,7 @@ bool KvAllocator::unmap_from_kv_tensors(const offset_t *offsets, size_t n) {
     sg.t = now_ns();
   }
   auto slots = slots_for(offsets, n);
-  sg.mark(10);
+  sg.mark(kSegUnmapOffsets);
   bool async = options().async_unmap.load() != 0; // also on the cpu device: same queue and thread, no driver calls
   for (auto &r : layers_) async = async && !r->backfilled; // compat mode promises zeros behind an unmap: stay synchronous
   if (async) {

@@ -22,7 +22,6 @@
 
 namespace kvc {
 
-constexpr unsigned kMaxLanesPerBuffer = 64; // KVCACHED_LANES_PER_BUFFER at most (a lane buffer is rows x lanes pages)
 
 // What backs a slot (KvRegion::mapped).
 enum SlotState : uint8_t {

@@ -28,7 +28,7 @@ void KvAllocator::setup_lanes() {
   rows_.clear();
   lane_pool_ = nullptr;
   if (!dev_.is_gpu || contiguous_ || exportable_ || layers_.empty() || !ctx_) return;
-  if (!env_bool("KVCACHED_LANE_EXTENTS", true) || options().phys_chunk_pages.load() <= 1) return;
+  if (!env_option("KVCACHED_LANE_EXTENTS") || options().phys_chunk_pages.load() <= 1) return;
   if (options().async_unmap.load()) return; // queued unmaps work slot by slot (the reclaimer's chunks): the per-slot path keeps them
   const bool kv = !unified_pool_ && num_kv_buffers_ == 2;
   for (auto &r : layers_) {
@@ -141,10 +141,10 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
         register_slot(reg, idx);
         stats().t_unmap_alias += now_ns() - t0;
       });
-  sg.mark(1);
+  sg.mark(kSegMapClassify);
   const std::vector<SlotRun> runs = scan.collect();
-  stats().seg[23] += (int64_t)runs.size();
-  sg.mark(2);
+  stats().seg[kSegMapRunCount] += (int64_t)runs.size();
+  sg.mark(kSegMapRuns);
 
   struct Chunk {
     size_t p, k, rows_done;
@@ -168,16 +168,16 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
         const int64_t t1 = now_ns();
         c.k = acquire_pages(pool, end - at, c.lane, /*stolen=*/nullptr); // (a stolen page is not a lane)
         const int64_t t2 = now_ns();
-        sg.mark(3);
+        sg.mark(kSegMapPool);
         unsigned j0 = 0, ke = 1;
         void *bo = vmm_direct_bo(c.lane[0].h, &j0, &ke);
         if (!bo) throw GpuError("a lane's buffer is not a direct DRM buffer");
         if (const int rc = back_rows(bo, j0, ke, at, c.k, split, c.rows_done))
           throw GpuError(std::string("DRM_AMDGPU_GEM_VA (backing a page id) failed: ") + strerror(rc < 0 ? -rc : rc));
-        stats().seg[21] += (int64_t)R;
+        stats().seg[kSegMapIoctlCount] += (int64_t)R;
         stats().t_acquire += t2 - t1;
         stats().t_map += now_ns() - t2;
-        sg.mark(4);
+        sg.mark(kSegMapIoctls);
         for (size_t j = 0; j < c.k; ++j) {
           max_ticket = std::max(max_ticket, c.lane[j].wait_ticket);
           const bool clean = fill && c.lane[j].scrub_ticket != 0;
@@ -195,22 +195,22 @@ bool KvAllocator::try_map_lanes(const offset_t *offsets, size_t n) {
         c.settled = true;
         ids += c.k;
         at += c.k;
-        sg.mark(5);
+        sg.mark(kSegMapBookkeeping);
       }
     }
     // (no flush happens between the REPLACEs of this path, so they are all noted here, once)
     settle_batch(ctx, ps, split.prt_dirty, split.zx_dirty, need_epoch, split.replaced || options().map_shootdown_always.load() != 0);
-    sg.mark(6);
+    sg.mark(kSegMapInvalidation);
     const int64_t ts = now_ns();
     for (size_t i = 0; i < pending.size(); i += kMaxPtrsPerLaunch) { // fresh memory, or pages that came back unscrubbed
       ctx->zero_fill(pending.data() + i, std::min<size_t>(kMaxPtrsPerLaunch, pending.size() - i), ps, nullptr);
       launched = true;
     }
     if (launched) ctx->sync(nullptr);
-    sg.mark(7);
+    sg.mark(kSegMapWaitFill);
     ctx->wait_scrub(max_ticket);
     stats().t_sync += now_ns() - ts;
-    sg.mark(8);
+    sg.mark(kSegMapWaitScrub);
   } catch (...) {
     roll_back(ctx, launched, [&]() {
       for (auto it = done.rbegin(); it != done.rend(); ++it) {
@@ -245,7 +245,7 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
   ctx->bind();
   ExtentPool *pool = lane_pool_;
   const std::vector<SlotRun> runs = scan.collect();
-  sg.mark(11);
+  sg.mark(kSegUnmapRuns);
   Unmapped u; // own: the lanes that go home
   u.pool = pool;
   u.rows = R;
@@ -261,12 +261,12 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
         for_rest_pieces(reg, rows_[r].first + p0, run.count, [&](size_t first, size_t cnt) {
           const int rc = rest_replace(reg, first, cnt);
           if (rc != 0) throw GpuError(std::string("DRM_AMDGPU_GEM_VA replace (back to the rest state) failed: ") + strerror(rc < 0 ? -rc : rc));
-          stats().seg[22]++;
+          stats().seg[kSegUnmapIoctlCount]++;
         });
         u.any_backfilled = u.any_backfilled || reg.backfilled;
       } else {
         vmm_unmap_run(reg.base + (rows_[r].first + p0) * ps, run.count * ps);
-        stats().seg[22]++;
+        stats().seg[kSegUnmapIoctlCount]++;
       }
       stats().t_unmap += now_ns() - t0;
     }
@@ -281,10 +281,10 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
       ++touched.at(chunk_of(h));
     }
   }
-  sg.mark(12);
+  sg.mark(kSegUnmapIoctls);
   for (const SlotRun &run : runs)
     for_rows(run.first - rows_[0].first, [&](KvRegion &reg, size_t first) { std::fill(reg.mapped.begin() + first, reg.mapped.begin() + first + run.count, Unbacked); });
-  sg.mark(13);
+  sg.mark(kSegUnmapBookkeeping);
   // Lanes that were backed together share one mapping per row; taking some of them out splits it, and what is left of it
   // must be written again before the invalidation (DrmVm::refresh_mappings_of, §4.8). A buffer that loses ALL its mapped
   // lanes here leaves nothing behind.
@@ -298,11 +298,11 @@ size_t KvAllocator::unmap_lanes(const offset_t *offsets, size_t n, std::vector<o
         }
     if (any) tlb_stale().store(true);
   }
-  sg.mark(14);
+  sg.mark(kSegUnmapRemainders);
   const uint64_t epoch = u.epoch = ctx->next_flush_epoch(); // every driver call that removed or rewrote a translation has returned
   for (const SlotRun &run : runs)
     for_rows(run.first - rows_[0].first, [&](KvRegion &reg, size_t first) { std::fill(reg.stale_epoch.begin() + first, reg.stale_epoch.begin() + first + run.count, epoch); });
-  sg.mark(15);
+  sg.mark(kSegUnmapEpochs);
   // a peer's memory: no translation of it may survive the call (one entry per page id: the buffer goes - behind the
   // invalidation - when the last page id it backs here has gone)
   u.foreign = !peers_buffers.empty();
@@ -422,7 +422,7 @@ bool KvAllocator::map_imported_page_ids(const offset_t *offsets, size_t n, const
         std::fill(reg.mapped.begin() + idx, reg.mapped.begin() + idx + cnt, PeerLane);
       });
       d.settled = true;
-      stats().seg[21] += (int64_t)R;
+      stats().seg[kSegMapIoctlCount] += (int64_t)R;
       i += cnt;
     }
     settle_batch(ctx, ps, split.prt_dirty, split.zx_dirty, need_epoch, split.replaced);

@@ -77,7 +77,7 @@ void settle_batch(GpuContext *ctx, size_t ps, bool &prt_dirty, void *&zx_dirty, 
     zx_dirty = nullptr;
     replaced = true;
   }
-  stats().seg[20] += now_ns() - t_rw;
+  stats().seg[kSegMapRemainderRewrite] += now_ns() - t_rw;
   if (replaced) {
     tlb_stale().store(true);
     need_epoch = ctx->next_flush_epoch();
@@ -299,8 +299,8 @@ struct KvAllocator::MapBatch {
   // The fresh slots, run by run: as many neighbours as one extent can serve at a time, one ioctl each
   void back_runs(const std::vector<SlotRun> &runs) {
     std::vector<Phys> got(kMaxExtentPages);
-    stats().seg[23] += (int64_t)runs.size();
-    sg.mark(2);
+    stats().seg[kSegMapRunCount] += (int64_t)runs.size();
+    sg.mark(kSegMapRuns);
     for (const SlotRun &run : runs) {
       KvRegion &r = *run.r;
       // A region whose map path owes no invalidation (lazy mode: plain unmapped VA behind unbacked slots) keeps its mappings
@@ -312,12 +312,12 @@ struct KvAllocator::MapBatch {
       const size_t max_run = r.rest_direct() ? (size_t)-1 : std::max<size_t>(1, (512u << 20) / ps);
       for (size_t at = run.first, end = run.first + run.count; at < end;) {
         const int64_t t1 = now_ns();
-        sg.mark(5);
+        sg.mark(kSegMapBookkeeping);
         bool stolen = false;
         const size_t n = a.acquire_pages(pool, std::min(end - at, max_run), got.data(), &stolen);
         if (stolen) need_epoch = ctx->next_flush_epoch(); // (its unmap has set tlb_stale: flushed before the fill)
         const int64_t t2 = now_ns();
-        sg.mark(3);
+        sg.mark(kSegMapPool);
         char *va = r.base + at * ps;
         try {
           if (r.rest_direct()) { // the slots carry their rest mapping: pages take its place in the same ioctl
@@ -332,8 +332,8 @@ struct KvAllocator::MapBatch {
         }
         stats().t_acquire += t2 - t1;
         stats().t_map += now_ns() - t2;
-        stats().seg[21]++;
-        sg.mark(4);
+        stats().seg[kSegMapIoctlCount]++;
+        sg.mark(kSegMapIoctls);
         // (per page of the batch: everything this loop updates is a local or the regions' arrays - nothing is re-read
         // through `this` - and nothing in it can throw while `done` has entries that are not filled in yet)
         const bool want_fill = fill;
@@ -362,17 +362,17 @@ struct KvAllocator::MapBatch {
 
   // the last fills, the invalidation if one is still owed, and the wait for everything that was launched or was in flight
   void finish() {
-    sg.mark(5);
+    sg.mark(kSegMapBookkeeping);
     if (fill) launch_pending(true);
     settle(); // nothing may reach the new mappings through a stale translation of their own addresses
-    sg.mark(6);
+    sg.mark(kSegMapInvalidation);
     const int64_t ts = now_ns();
     if (launched) ctx->sync(nullptr);
-    sg.mark(7);
+    sg.mark(kSegMapWaitFill);
     ctx->wait_scrub(max_ticket);
     stats().t_sync += now_ns() - ts;
-    sg.mark(8);
-    if (max_ticket) stats().seg[9] += (int64_t)(ctx->scrubs_issued() - max_ticket); // (diagnostics: how many scrubs behind the newest the one waited for was)
+    sg.mark(kSegMapWaitScrub);
+    if (max_ticket) stats().seg[kSegMapScrubsBehind] += (int64_t)(ctx->scrubs_issued() - max_ticket); // (diagnostics: how many scrubs behind the newest the one waited for was)
   }
 
   // leave the regions as they were before this call; PageAllocator rolls the page ids back
@@ -444,7 +444,7 @@ void KvAllocator::map_slots(const std::vector<Slot> &slots, const std::vector<ph
       }
     }
     b.flush_run();
-    b.sg.mark(1);
+    b.sg.mark(kSegMapClassify);
     if (fresh.size()) b.back_runs(fresh.collect());
     b.finish();
   } catch (...) {
@@ -531,13 +531,13 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
         if (scan.add(&r, slots[i].index)) cleared[i] = 2; // (2: and its extent is counted in `touched` with its run)
     }
     const std::vector<SlotRun> runs = scan.collect([](const KvRegion &r) { return r.rest_group(); });
-    sg.mark(11);
+    sg.mark(kSegUnmapRuns);
     for (const SlotRun &run : runs) {
       const int64_t t0 = now_ns();
       const int rc = rest_replace(*run.r, run.first, run.count);
       if (rc != 0) throw GpuError(std::string("DRM_AMDGPU_GEM_VA replace (back to the rest state) failed: ") + strerror(rc < 0 ? -rc : rc));
       stats().t_unmap += now_ns() - t0;
-      stats().seg[22]++;
+      stats().seg[kSegUnmapIoctlCount]++;
       // the extents these pages belong to, in address order: neighbours share theirs, so the list stays short
       if (own_direct)
         for (size_t k = run.first; k < run.first + run.count; ++k) {
@@ -546,7 +546,7 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
         }
     }
   }
-  sg.mark(12);
+  sg.mark(kSegUnmapIoctls);
   size_t max_clear = (size_t)options().clear_run_slots.load();
   if (max_clear >= 2 && xpool->multi_page()) max_clear = std::max<size_t>(max_clear, xpool->max_extent_pages()); // a whole extent in one go
   if (max_clear >= 2 && vmm_backend() == kVmmDrm && DrmVm::instance().can_clear()) {
@@ -606,7 +606,7 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
   }
   flush_run();
   u.foreign = !u.imported.empty();
-  sg.mark(13);
+  sg.mark(kSegUnmapBookkeeping);
   if (!touched.items().empty() && !KVC_TEST_HOOK("SKIP_REMAINDER_REFRESH")) { // hook: prove the test has teeth
     for (auto &kv : touched.items()) {
       // pieces still handed out beyond the ones this batch takes back = pages of the extent that stay mapped
@@ -616,13 +616,13 @@ void KvAllocator::unmap_collect(const std::vector<Slot> &slots, Unmapped &u) {
     }
     tlb_stale().store(true);
   }
-  sg.mark(14);
+  sg.mark(kSegUnmapRemainders);
   { // every driver call that removed or rewrote a translation has returned: the next invalidation to START covers them all
     const uint64_t epoch = ctx->next_flush_epoch();
     for (auto &g : gone) g.first->stale_epoch[g.second] = epoch;
     u.epoch = epoch;
   }
-  sg.mark(15);
+  sg.mark(kSegUnmapEpochs);
 }
 
 namespace {
@@ -681,7 +681,7 @@ void KvAllocator::unmap_finish(Unmapped &u, bool may_defer_shootdown) {
       pool->release_batch(own->data(), own->size(), scrub_on_the_way_back(ctx, pool, *own, rows, ps));
     });
     ctx->request_async_flush(trail_us);
-    sg.mark(16);
+    sg.mark(kSegUnmapInvalidation);
     stats().pages_unmapped += u.n;
     return;
   }
@@ -697,12 +697,12 @@ void KvAllocator::unmap_finish(Unmapped &u, bool may_defer_shootdown) {
   for (auto h : u.imported) {
     if (!vmm_try_release(h)) KVC_LOG(LOG_ERROR, "releasing an imported handle failed");
   }
-  sg.mark(16);
+  sg.mark(kSegUnmapInvalidation);
   const int64_t tr0 = now_ns();
   const uint64_t ticket = scrub_on_the_way_back(ctx, pool, u.own, u.rows, u.page_size);
-  sg.mark(17);
+  sg.mark(kSegUnmapScrubLaunch);
   pool->release_batch(u.own.data(), u.own.size(), ticket);
-  sg.mark(18);
+  sg.mark(kSegUnmapPool);
   stats().t_release += now_ns() - tr0;
   stats().pages_unmapped += u.n;
 }

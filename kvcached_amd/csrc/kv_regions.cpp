@@ -46,7 +46,7 @@ std::unique_ptr<KvRegion> KvAllocator::make_region(const std::string &name, size
 // contract (nothing touches unbacked VA) is what makes its map path free of one: plain unmapped VA, where a violation
 // faults instead of poisoning the next mapping. KVCACHED_PRT=true|false overrides either default.
 bool KvAllocator::prt_all(KvRegion &r, bool by_default) {
-  if (!dev_.is_gpu || vmm_backend() != kVmmDrm || !DrmVm::instance().can_clear() || !env_bool("KVCACHED_PRT", by_default)) return false;
+  if (!dev_.is_gpu || vmm_backend() != kVmmDrm || !DrmVm::instance().can_clear() || !env_flag("KVCACHED_PRT", by_default)) return false;
   hipDeviceProp_t prop{};
   if (hipGetDeviceProperties(&prop, ctx_->dev()) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
     (void)hipGetLastError();
@@ -97,7 +97,7 @@ void KvAllocator::backfill_all(KvRegion &r) {
   }
   // drm backend: one buffer of zeros, a whole group of slots aliased per ioctl, no per-slot object anywhere (§4.2):
   // 2 304 ioctls for the 147 k slots of a 288 GiB reservation instead of 147 k map + set_access pairs.
-  if (env_bool("KVCACHED_ZERO_EXTENT", true)) {
+  if (env_option("KVCACHED_ZERO_EXTENT")) {
     size_t zp = 0;
     if (const phys_handle_t zh = ctx_->zero_extent(r.page_size, &zp)) {
       void *zbo = DrmVm::instance().find(zh);

@@ -147,7 +147,7 @@ bool drm_self_test(int dev) {
     if (vm.unmap(bo_b, va, ps) != 0) throw 23;
     drm_mapped = nullptr;
     bool kfd_ok = false;
-    if (env_bool("KVCACHED_DRM_KFD_CREATE", true) && !KVC_TEST_HOOK("FAIL_KFD_SELFTEST")) {
+    if (env_option("KVCACHED_DRM_KFD_CREATE") && !KVC_TEST_HOOK("FAIL_KFD_SELFTEST")) {
       std::string why_kfd;
       phys_handle_t k = 0;
       int step = 0;

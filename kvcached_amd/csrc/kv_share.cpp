@@ -19,7 +19,7 @@ std::atomic<int64_t> g_imports_direct{0}, g_imports_runtime{0}; // pages importe
 int64_t import_count(bool direct) { return direct ? g_imports_direct.load() : g_imports_runtime.load(); }
 static phys_handle_t import_posix_fd(int fd) {
   if (fd < 0 || fcntl(fd, F_GETFD) == -1) throw InvalidError("import of an invalid file descriptor");
-  if (vmm_backend() == kVmmDrm && DrmVm::instance().kfd_ready() && env_bool("KVCACHED_DRM_KFD_IMPORT", true)) {
+  if (vmm_backend() == kVmmDrm && DrmVm::instance().kfd_ready() && env_option("KVCACHED_DRM_KFD_IMPORT")) {
     // straight into KFD + DRM: mapped with one ioctl like our own pages. A buffer that lives on ANOTHER GPU (rank 0's
     // pages seen from a peer over xGMI) may be refused by this shortcut - ROCr's import, which sets up peer access for
     // the local agent, is the fallback (hsa_amd_vmem_import_shareable_handle + map + set_access below).

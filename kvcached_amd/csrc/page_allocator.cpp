@@ -11,18 +11,11 @@ namespace kvc {
 namespace {
 // Environment defaults are read once per process like the reference's file-scope constants (:24-37).
 int64_t env_min_reserved() {
-  static const int64_t v = env_i64("KVCACHED_MIN_RESERVED_PAGES", 5);
+  static const int64_t v = env_option("KVCACHED_MIN_RESERVED_PAGES");
   return v;
 }
 int64_t env_max_reserved() {
-  static const int64_t v = env_i64("KVCACHED_MAX_RESERVED_PAGES", 10);
-  return v;
-}
-double env_gpu_utilization() {
-  static const double v = []() {
-    const char *e = std::getenv("KVCACHED_GPU_UTILIZATION");
-    return e ? std::atof(e) : 0.95;
-  }();
+  static const int64_t v = env_option("KVCACHED_MAX_RESERVED_PAGES");
   return v;
 }
 } // namespace

@@ -373,7 +373,7 @@ def share_mapped_slots(tp_size: int, offsets: List[int], pp_rank: int = 0, group
     # page ids as units where the library backs them as lanes (one dmabuf per buffer: DESIGN.md §4.11), slot by slot otherwise
     # (single-row geometries, other backends, KVCACHED_EXPORTABLE_HANDLES=1)
     meta = None
-    if capi.get_option(129) > 0:
+    if capi.get_option(capi.OPT_LANES_PER_BUFFER) > 0:
         try:
             fds, meta = capi.export_page_ids(offsets, group_id)
         except capi.KvcError:

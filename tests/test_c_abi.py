@@ -102,7 +102,7 @@ def test_backend_names_are_validated(monkeypatch):
         try:
             ts = vmm_ops.create_kv_tensors(4 << 20, 1, "cpu", 1)
             assert vmm_ops.map_to_kv_tensors([0]) and vmm_ops.unmap_from_kv_tensors([0])
-            assert capi.get_option(110) == 0                     # pages straight from KFD: only ever on a GPU
+            assert capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) == 0                     # pages straight from KFD: only ever on a GPU
         finally:
             vmm_ops.shutdown_kvcached()
 

@@ -14,7 +14,6 @@ MiB = 1 << 20
 PAGE = 2 * MiB
 DEV = "cuda:0"
 WORDS = PAGE // 4
-OPT_MAP_IOCTLS, OPT_UNMAP_IOCTLS, OPT_CREATES = 151, 152, 115
 
 
 @pytest.fixture()
@@ -28,7 +27,7 @@ def compat():
     finally:
         os.environ.pop("KVCACHED_ZERO_BACKFILL", None)
     t = vmm_ops.create_kv_tensors(4096 * PAGE, 2, DEV, 1, 1, 0, True)[0]
-    if capi.get_option(108) != 3 or capi.get_option(110) != 1:
+    if capi.get_option(capi.OPT_EFFECTIVE_BACKEND) != 3 or capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) != 1:
         vmm_ops.shutdown_kvcached()
         pytest.skip("needs the drm backend with pages straight from KFD")
     assert capi.get_option(capi.OPT_MAX_EXTENT_PAGES) == 1024
@@ -50,20 +49,20 @@ def test_a_compat_batch_of_1024_slots_is_one_ioctl_each_way(compat):
     ops, capi, slots = compat
     capi.reset_stats()
     assert ops.map_to_kv_tensors(_slots(1024, 1024))
-    assert capi.get_option(OPT_MAP_IOCTLS) == 1
+    assert capi.get_option(capi.OPT_SEG_MAP_IOCTL_COUNT) == 1
     assert int(torch.count_nonzero(slots[1024:2048])) == 0
-    creates = capi.get_option(OPT_CREATES)
+    creates = capi.get_option(capi.OPT_KFD_CREATES)
     slots[1024:2048] = 7
     torch.cuda.synchronize()
     capi.reset_stats()
     assert ops.unmap_from_kv_tensors(_slots(1024, 1024, 1))
-    assert capi.get_option(OPT_UNMAP_IOCTLS) == 1
+    assert capi.get_option(capi.OPT_SEG_UNMAP_IOCTL_COUNT) == 1
     assert int(torch.count_nonzero(slots[1024:2048])) == 0          # compat: a freed slot reads zero when unmap returns
     capi.reset_stats()
     assert ops.map_to_kv_tensors(_slots(2048, 1024, 2))               # other slots, the same 2 GiB extent
     st = capi.get_stats()
-    assert capi.get_option(OPT_MAP_IOCTLS) == 1 and st["handles_created"] == 0 and st["handles_reused"] == 1024
-    assert capi.get_option(OPT_CREATES) == creates
+    assert capi.get_option(capi.OPT_SEG_MAP_IOCTL_COUNT) == 1 and st["handles_created"] == 0 and st["handles_reused"] == 1024
+    assert capi.get_option(capi.OPT_KFD_CREATES) == creates
     assert int(torch.count_nonzero(slots[2048:3072])) == 0           # recycled, dirty, zero again
     assert ops.unmap_from_kv_tensors(_slots(2048, 1024))
 
@@ -79,7 +78,7 @@ def test_a_page_out_of_the_middle_of_a_1024_page_extent(compat):
         torch.cuda.synchronize()
         capi.reset_stats()
         assert ops.unmap_from_kv_tensors([mid * PAGE])
-        assert capi.get_option(OPT_UNMAP_IOCTLS) == 1
+        assert capi.get_option(capi.OPT_SEG_UNMAP_IOCTL_COUNT) == 1
         assert int(torch.count_nonzero(slots[mid])) == 0
         assert int(slots[mid - 1:mid + 2].sum()) == before - (mid + 1) * WORDS
         assert ops.map_to_kv_tensors([mid * PAGE])                    # backed again: whichever page, it reads zero
@@ -96,7 +95,7 @@ def test_single_slots_out_of_a_1024_slot_prt_mapping_whose_neighbours_were_read(
     assert ops.map_to_kv_tensors(_slots(1024, 1024))
     capi.reset_stats()
     assert ops.unmap_from_kv_tensors(_slots(1024, 1024))
-    assert capi.get_option(OPT_UNMAP_IOCTLS) == 1                     # one PRT mapping of 1024 slots now
+    assert capi.get_option(capi.OPT_SEG_UNMAP_IOCTL_COUNT) == 1                     # one PRT mapping of 1024 slots now
     for round_, picks in enumerate(([1024 + 300], [1024 + 301, 1024 + 700], [1024 + 1, 1024 + 1022])):
         assert int(torch.count_nonzero(slots[1024:2048])) == 0       # every neighbour looked at: PRT entries in the TLBs
         torch.cuda.synchronize()

@@ -337,7 +337,7 @@ def test_offload_a_page_id_of_the_engine_geometry(lib, monkeypatch):
     ops, capi = lib
     os.environ["KVCACHED_PHYS_RESERVE_MB"] = "0"
     m, views = _manager_setup(ops, monkeypatch, "per_layer", n_pages=16, layers=32)
-    assert capi.get_option(129) > 0                               # page ids are backed by lanes
+    assert capi.get_option(capi.OPT_LANES_PER_BUFFER) > 0                               # page ids are backed by lanes
     bpp = views[0].shape[0] // 16
     ids = m.alloc(bpp * 4)
     _stamp(views, ids)

@@ -66,9 +66,9 @@ def _check(views, ids, base):
 def test_page_ids_are_backed_and_given_back_as_units(lanes, compat, unified):
     ops, capi, views = _engine(lanes, layers=8 if unified else 4, ids_per_half=64, compat=compat, unified=unified)
     R = len(views)
-    assert R == 8 and capi.get_option(129) == 8          # page ids are backed by lanes, 8 to a buffer at most
+    assert R == 8 and capi.get_option(capi.OPT_LANES_PER_BUFFER) == 8          # page ids are backed by lanes, 8 to a buffer at most
     capi.reset_stats()                                   # once: the ledger at the end counts from here
-    snap = lambda: (capi.get_stats()["pages_mapped"], capi.get_option(130 + 21), capi.get_option(130 + 23))   # noqa: E731  pages, ioctls, runs
+    snap = lambda: (capi.get_stats()["pages_mapped"], capi.get_option(capi.OPT_SEG_MAP_IOCTL_COUNT), capi.get_option(capi.OPT_SEG_MAP_RUN_COUNT))   # noqa: E731  pages, ioctls, runs
     delta = lambda a, b: tuple(y - x for x, y in zip(a, b))                                                     # noqa: E731
     # one page id: R slots, R ioctls, one lane
     s0 = snap()
@@ -122,7 +122,7 @@ def test_page_ids_are_backed_and_given_back_as_units(lanes, compat, unified):
     for v in views:
         assert int(torch.count_nonzero(v[7:10])) == 0
     assert ops.unmap_from_kv_tensors([p * PAGE for p in (7, 8, 9)])
-    assert capi.get_option(124) == 0                     # no release the pool did not know
+    assert capi.get_option(capi.OPT_POOL_BAD_RELEASES) == 0                     # no release the pool did not know
     ops.shutdown_kvcached()
     st = capi.get_stats()
     assert st["handles_created"] == st["handles_released"] and st["handles_created"] % R == 0
@@ -180,14 +180,14 @@ def test_a_call_the_lanes_cannot_take_goes_the_per_slot_way(lanes):
 
 def test_a_driver_failure_rolls_a_lane_batch_back(lanes):
     ops, capi, views = _engine(lanes, layers=2, ids_per_half=32, compat=True, lane_mb=16)    # 16 MiB buffers: 2 lanes each (4 rows x 2 MiB)
-    assert capi.get_option(129) == 2
+    assert capi.get_option(capi.OPT_LANES_PER_BUFFER) == 2
     capi.reset_stats()
     assert ops.map_to_kv_tensors([0])
     _stamp(views, [0], 50)
-    capi.set_option(104, 1)                                          # the second creation from now fails
+    capi.set_option(capi.OPT_FAIL_AFTER_CREATES, 1)                                          # the second creation from now fails
     with pytest.raises(RuntimeError):
         ops.map_to_kv_tensors([p * PAGE for p in range(10, 16)])     # 3 buffers of 2 lanes
-    capi.set_option(104, -1)
+    capi.set_option(capi.OPT_FAIL_AFTER_CREATES, -1)
     for v in views:                                                  # nothing of the batch is left behind
         assert int(torch.count_nonzero(v[10:16, ::4096])) == 0
     _check(views, [0], 50)
@@ -203,7 +203,7 @@ def test_a_driver_failure_rolls_a_lane_batch_back(lanes):
 def test_lanes_can_be_switched_off(lanes, monkeypatch):
     monkeypatch.setenv("KVCACHED_LANE_EXTENTS", "false")
     ops, capi, views = _engine(lanes, layers=2, ids_per_half=16, compat=True)
-    assert capi.get_option(129) == 0
+    assert capi.get_option(capi.OPT_LANES_PER_BUFFER) == 0
     capi.reset_stats()
     assert ops.map_to_kv_tensors([3 * PAGE])
     assert capi.get_stats()["pages_mapped"] == len(views)
@@ -232,7 +232,7 @@ def test_the_unmap_side_invalidation_may_trail_the_call_but_pages_wait_for_it(la
         views, R = [], 2 * layers
         for t in ts:
             views += [t[:64 * EPP].view(64, EPP), t[64 * EPP:].view(64, EPP)]
-    assert capi.get_option(capi.OPT_UNMAP_INVALIDATION_US) == 400 and (capi.get_option(129) > 0) == (layers > 1)
+    assert capi.get_option(capi.OPT_UNMAP_INVALIDATION_US) == 400 and (capi.get_option(capi.OPT_LANES_PER_BUFFER) > 0) == (layers > 1)
     a, b = list(range(0, 8)), list(range(20, 28))
     capi.reset_stats()                                                       # once: the ledger at the end counts from here
     assert ops.map_to_kv_tensors([p * PAGE for p in a])
@@ -269,7 +269,7 @@ def test_the_unmap_side_invalidation_may_trail_the_call_but_pages_wait_for_it(la
     assert cycles <= 6 + 2, cycles                                           # (strict compat: 12)
     assert ops.unmap_from_kv_tensors([p * PAGE for p in (b if rnd % 2 == 0 else a)])
     capi.flush_unmaps()
-    assert capi.get_option(124) == 0
+    assert capi.get_option(capi.OPT_POOL_BAD_RELEASES) == 0
     ops.shutdown_kvcached()
     st = capi.get_stats()
     assert st["handles_created"] == st["handles_released"]
@@ -383,12 +383,12 @@ def test_page_ids_are_shared_as_units(lanes, compat):
     fds, meta = capi.export_page_ids([p * PAGE for p in ids], 0)
     # two buffers: the run of three (three lanes, in order) and the single one
     assert len(fds) == 2 and meta == [0, 3, 0, 0, 3, 1, 0, 3, 2, 1, 1, 0], meta
-    i0 = capi.get_option(130 + 21)
+    i0 = capi.get_option(capi.OPT_SEG_MAP_IOCTL_COUNT)
     m0 = capi.get_stats()["pages_mapped"]
     capi.map_imported_page_ids([p * PAGE for p in ids], fds, meta, 1)
     for fd in fds:
         os.close(fd)
-    assert capi.get_stats()["pages_mapped"] - m0 == 4 * R and capi.get_option(130 + 21) - i0 == 2 * R   # one ioctl per row per run of neighbours
+    assert capi.get_stats()["pages_mapped"] - m0 == 4 * R and capi.get_option(capi.OPT_SEG_MAP_IOCTL_COUNT) - i0 == 2 * R   # one ioctl per row per run of neighbours
     _check(vb, ids, 4000)                                              # the peer sees the owner's bytes, row by row, page id by page id
     vb[R - 1][5][100:116] = 77                                         # ... and writes into the same memory
     torch.cuda.synchronize()

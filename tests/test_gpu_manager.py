@@ -323,20 +323,20 @@ def test_driver_failure_rolls_the_batch_back(monkeypatch):
         first = m.alloc(10)
         before = (m.available_size(), m.page_allocator.get_num_free_pages(), m.page_allocator._page_list(0))
         capi.reset_stats()
-        capi.set_option(104, 5)                         # page id 1 needs 8 slots; the 6th create fails
+        capi.set_option(capi.OPT_FAIL_AFTER_CREATES, 5)                         # page id 1 needs 8 slots; the 6th create fails
         with pytest.raises(RuntimeError, match=r"Failed to map page 1: .*hipMemCreate.*\[injected\]"):
             m.alloc(100)
-        capi.set_option(104, -1)
+        capi.set_option(capi.OPT_FAIL_AFTER_CREATES, -1)
         st = capi.get_stats()
         assert st["handles_created"] == 5 and st["handles_released"] == 5      # the partial batch was undone
         after = (m.available_size(), m.page_allocator.get_num_free_pages(), m.page_allocator._page_list(0))
         assert after == before
         # the batched path: 300 blocks need 4 new page ids = 32 slots in ONE map call; the 21st create fails
         capi.reset_stats()
-        capi.set_option(104, 20)
+        capi.set_option(capi.OPT_FAIL_AFTER_CREATES, 20)
         with pytest.raises(RuntimeError, match=r"Failed to map page 1: .*hipMemCreate.*\[injected\]"):
             m.alloc(300)
-        capi.set_option(104, -1)
+        capi.set_option(capi.OPT_FAIL_AFTER_CREATES, -1)
         st = capi.get_stats()
         assert st["handles_created"] == 20 and st["handles_released"] == 20
         after = (m.available_size(), m.page_allocator.get_num_free_pages(), m.page_allocator._page_list(0))
@@ -348,7 +348,7 @@ def test_driver_failure_rolls_the_batch_back(monkeypatch):
         m.free(first + got)
         del m
     finally:
-        capi.set_option(104, -1)
+        capi.set_option(capi.OPT_FAIL_AFTER_CREATES, -1)
         vmm_ops.shutdown_kvcached()
 
 
@@ -398,7 +398,7 @@ def test_the_physical_reserve_is_created_ahead_of_time_and_serves_a_growth_burst
         vmm_ops.create_kv_tensors(256 * T.PAGE * 2, 1, DEV, 2, 2, 0, False)
         m = kcm.KVCacheManager(num_blocks=256 * 64, block_size=16, cell_size=2048, num_layers=2)
         assert m._post_init_done.wait(10)
-        if capi.get_option(108) != 3 or capi.get_option(110) != 1:
+        if capi.get_option(capi.OPT_EFFECTIVE_BACKEND) != 3 or capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) != 1:
             pytest.skip("the reserve is pre-created with the drm backend and pages straight from KFD")
         t0 = time.time()
         while time.time() - t0 < 5:                                  # a few 100 ms ticks (256 pages per tick at most)
@@ -448,7 +448,7 @@ def test_the_reserve_follows_demand(monkeypatch):
         vmm_ops.create_kv_tensors(512 * T.PAGE * 2, 1, DEV, L, 2, 0, False)
         m = kcm.KVCacheManager(num_blocks=512 * 64, block_size=16, cell_size=2048, num_layers=L)
         assert m._post_init_done.wait(10)
-        if capi.get_option(108) != 3 or capi.get_option(110) != 1:
+        if capi.get_option(capi.OPT_EFFECTIVE_BACKEND) != 3 or capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) != 1:
             pytest.skip("the reserve is pre-created with the drm backend and pages straight from KFD")
         rows = 2 * L
         time.sleep(0.5)
@@ -493,7 +493,7 @@ def test_an_idle_engine_gives_its_reserve_back(monkeypatch):
         vmm_ops.create_kv_tensors(128 * T.PAGE * 2, 1, DEV, 4, 2, 0, False)
         m = kcm.KVCacheManager(num_blocks=128 * 64, block_size=16, cell_size=2048, num_layers=4)
         assert m._post_init_done.wait(10)
-        if capi.get_option(108) != 3 or capi.get_option(110) != 1:
+        if capi.get_option(capi.OPT_EFFECTIVE_BACKEND) != 3 or capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) != 1:
             pytest.skip("the reserve is pre-created with the drm backend and pages straight from KFD")
         # whole idle buffers (free lanes of a buffer that a still-mapped page id pins cannot go back: they are handed out first instead)
         idle = lambda: capi.get_option(capi.OPT_POOL_HELD_PAGES) - capi.get_option(capi.OPT_POOL_OUT_PAGES) - capi.get_option(capi.OPT_POOL_FREE_PIECES)   # noqa: E731

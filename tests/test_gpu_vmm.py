@@ -150,11 +150,11 @@ def test_pages_are_private_and_zeroed_in_every_shipped_configuration(vmm, monkey
         monkeypatch.setenv(*switch.split("="))
     ops, capi, ts = _setup(vmm, layers=2, per_layer=64 * PAGE, backfill=(mode == "compat"), kv=1, unified=False)
     lanes_expected = backend == "drm" and extent_pages > 1 and not async_unmap and switch != "KVCACHED_LANE_EXTENTS=false"
-    assert (capi.get_option(129) > 0) == lanes_expected, capi.get_option(129)
+    assert (capi.get_option(capi.OPT_LANES_PER_BUFFER) > 0) == lanes_expected, capi.get_option(capi.OPT_LANES_PER_BUFFER)
     # PRT behind unbacked VA: the compat default on the drm backend; lazy mode leaves unbacked VA unmapped unless asked
     assert capi.get_option(capi.OPT_PRT) == int(backend == "drm" and (switch == "KVCACHED_PRT=true" or (mode == "compat" and switch != "KVCACHED_PRT=false")))
     want_backend = {"drm": 3, "hybrid": 2, "hip": 0}[backend]
-    assert capi.get_option(108) == want_backend
+    assert capi.get_option(capi.OPT_EFFECTIVE_BACKEND) == want_backend
     assert capi.get_option(capi.OPT_ASYNC_UNMAP) == async_unmap
     capi.reset_stats()
     n, epp = 64, PAGE // 2
@@ -302,7 +302,7 @@ def test_map_batches_invalidate_only_when_a_stale_translation_can_exist(vmm, mon
         else:
             monkeypatch.delenv("KVCACHED_PRT", raising=False)
         ops, capi, ts = _setup(vmm, layers=1, per_layer=64 * MiB, backfill=(mode == "compat"), kv=1, unified=True)
-        assert capi.get_option(capi.OPT_PRT) == int(mode == "compat" and os.environ.get("KVCACHED_PRT") != "false" and capi.get_option(108) == 3)
+        assert capi.get_option(capi.OPT_PRT) == int(mode == "compat" and os.environ.get("KVCACHED_PRT") != "false" and capi.get_option(capi.OPT_EFFECTIVE_BACKEND) == 3)
         t = ts[0]
         capi.reset_stats()
         even = [s * PAGE for s in range(0, 32, 2)]
@@ -537,7 +537,7 @@ def test_run_sized_extents_keep_every_page_with_its_slot(vmm, monkeypatch, max_p
     import random
     monkeypatch.setenv("KVCACHED_PHYS_CHUNK_PAGES", str(max_pages))
     ops, capi, ts = _setup(vmm, layers=2, per_layer=192 * MiB, backfill=False, kv=1, unified=False)
-    if capi.get_option(108) != 3 or capi.get_option(110) != 1:
+    if capi.get_option(capi.OPT_EFFECTIVE_BACKEND) != 3 or capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) != 1:
         pytest.skip("needs the drm backend with pages straight from KFD")
     assert capi.get_option(capi.OPT_MAX_EXTENT_PAGES) == max_pages
     capi.reset_stats()
@@ -585,7 +585,7 @@ def test_a_batch_of_adjacent_slots_is_a_handful_of_ioctls(vmm):
     """The point of extents: 1024 adjacent 2 MiB slots are backed by 1024 / 32 buffers, mapped with as many ioctls and
     dropped with as many - against 1024 + 1024 with one buffer per page - and the same extents serve the next batch."""
     ops, capi, ts = _setup(vmm, layers=1, per_layer=4096 * PAGE, backfill=False, kv=1, unified=True)
-    if capi.get_option(108) != 3 or capi.get_option(110) != 1:
+    if capi.get_option(capi.OPT_EFFECTIVE_BACKEND) != 3 or capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) != 1:
         pytest.skip("needs the drm backend with pages straight from KFD")
     k = capi.get_option(capi.OPT_MAX_EXTENT_PAGES)
     assert k > 1
@@ -596,7 +596,7 @@ def test_a_batch_of_adjacent_slots_is_a_handful_of_ioctls(vmm):
     assert ops.map_to_kv_tensors(offs)
     st = capi.get_stats()
     assert st["handles_created"] == 1024 and capi.get_option(capi.OPT_POOL_FREE_PIECES) == 0
-    creates = capi.get_option(115)
+    creates = capi.get_option(capi.OPT_KFD_CREATES)
     t = ts[0]
     assert int(torch.count_nonzero(t[:1024 * PAGE // 2])) == 0
     t[:1024 * PAGE // 2] = 7
@@ -607,7 +607,7 @@ def test_a_batch_of_adjacent_slots_is_a_handful_of_ioctls(vmm):
     assert ops.map_to_kv_tensors(offs2)
     st = capi.get_stats()
     assert st["handles_created"] == 0 and st["handles_reused"] == 1024
-    assert capi.get_option(115) == creates                             # not one driver allocation
+    assert capi.get_option(capi.OPT_KFD_CREATES) == creates                             # not one driver allocation
     assert int(torch.count_nonzero(t[2048 * PAGE // 2:3072 * PAGE // 2])) == 0    # recycled, dirty, zero again
     assert ops.unmap_from_kv_tensors(offs2)
 
@@ -621,7 +621,7 @@ def test_pages_are_zeroed_on_their_way_back_not_on_their_way_out(vmm, monkeypatc
     for scrub in (True, False):
         monkeypatch.setenv("KVCACHED_SCRUB_ON_RELEASE", "true" if scrub else "false")
         ops, capi, ts = _setup(vmm, layers=1, per_layer=512 * PAGE, backfill=False, kv=1, unified=True)
-        if capi.get_option(108) != 3 or capi.get_option(110) != 1:
+        if capi.get_option(capi.OPT_EFFECTIVE_BACKEND) != 3 or capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) != 1:
             pytest.skip("needs the drm backend with pages straight from KFD")
         t = ts[0]
         offs = [i * PAGE for i in range(0, 96)] + [i * PAGE for i in (200, 202, 204)]
@@ -666,7 +666,7 @@ def test_the_first_creation_brings_the_reserve_along_and_a_cycle_never_waits_for
     pool hands out what has been idle longest, and the cycle alternates between two sets of pages."""
     monkeypatch.setenv("KVCACHED_PHYS_RESERVE_MB", "128")          # 64 pages
     ops, capi, ts = _setup(vmm, layers=1, per_layer=512 * PAGE, backfill=True, kv=1, unified=True)
-    if capi.get_option(108) != 3 or capi.get_option(110) != 1:
+    if capi.get_option(capi.OPT_EFFECTIVE_BACKEND) != 3 or capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) != 1:
         pytest.skip("needs the drm backend with pages straight from KFD")
     t, epp = ts[0], PAGE // 2
     offs = [i * PAGE for i in range(64)]
@@ -674,7 +674,7 @@ def test_the_first_creation_brings_the_reserve_along_and_a_cycle_never_waits_for
     assert ops.map_to_kv_tensors(offs)
     st = capi.get_stats()
     assert st["handles_created"] == 64 + 64                          # its own pages + the reserve
-    assert capi.get_option(120) == 128 and capi.get_option(121) == 64   # held / handed out
+    assert capi.get_option(capi.OPT_POOL_HELD_PAGES) == 128 and capi.get_option(capi.OPT_POOL_OUT_PAGES) == 64   # held / handed out
     first = set()
     for cycle in range(6):
         for o in offs:
@@ -702,7 +702,7 @@ try:
 except RuntimeError as e:
     print("INIT REFUSED:", e)
     sys.exit(0)
-print("INIT OK backend", capi.get_option(108), "kfd flush", capi.get_option(118))
+print("INIT OK backend", capi.get_option(capi.OPT_EFFECTIVE_BACKEND), "kfd flush", capi.get_option(capi.OPT_KFD_TLB_FLUSH_ACTIVE))
 vmm_ops.shutdown_kvcached()
 """
 
@@ -864,7 +864,7 @@ def test_default_backend_and_its_fallback_chain(vmm, monkeypatch):
         if hook:
             monkeypatch.setenv(hook, "1")
         ops, capi, ts = _setup(vmm, layers=1, per_layer=16 * MiB, backfill=False, kv=1, unified=True)
-        assert capi.get_option(108) == want
+        assert capi.get_option(capi.OPT_EFFECTIVE_BACKEND) == want
         assert ops.map_to_kv_tensors([0, 3 * PAGE])
         assert int(torch.count_nonzero(ts[0][3 * epp:4 * epp])) == 0
         ts[0][:epp].fill_(321)
@@ -888,8 +888,8 @@ def test_drm_backend_one_ioctl_per_map_and_its_fallback(vmm, monkeypatch):
         if kfd_create == "selftest fails":
             monkeypatch.setenv("KVCACHED_TEST_FAIL_KFD_SELFTEST", "1")
         ops, capi, ts = _setup(vmm, layers=1, per_layer=64 * MiB, backfill=backfill, kv=1, unified=True)
-        assert capi.get_option(108) == 3
-        assert capi.get_option(110) == int(kfd_create is True)         # physical pages straight from KFD, or via ROCr
+        assert capi.get_option(capi.OPT_EFFECTIVE_BACKEND) == 3
+        assert capi.get_option(capi.OPT_KFD_CREATE_ACTIVE) == int(kfd_create is True)         # physical pages straight from KFD, or via ROCr
         capi.reset_stats()
         epp = PAGE // 2
         t = ts[0]
@@ -915,14 +915,14 @@ def test_drm_backend_one_ioctl_per_map_and_its_fallback(vmm, monkeypatch):
         for i in (7, 8, 20, 21, 22, 23):
             assert int(torch.count_nonzero(t[i * epp:(i + 1) * epp])) == 0
         st = capi.get_stats()
-        assert st["handles_reused"] >= 5 and st["pages_mapped"] == 11, (backfill, kfd_create, st, capi.get_option(124))
+        assert st["handles_reused"] >= 5 and st["pages_mapped"] == 11, (backfill, kfd_create, st, capi.get_option(capi.OPT_POOL_BAD_RELEASES))
         assert ops.unmap_from_kv_tensors(offs2)
         ops.shutdown_kvcached()
         st = capi.get_stats()
         assert st["handles_created"] == st["handles_released"]
     monkeypatch.setenv("KVCACHED_TEST_FAIL_DRM_SELFTEST", "1")
     ops, capi, ts = _setup(vmm, layers=1, per_layer=16 * MiB, backfill=False, kv=1, unified=True)
-    assert capi.get_option(108) == 2                                   # hybrid
+    assert capi.get_option(capi.OPT_EFFECTIVE_BACKEND) == 2                                   # hybrid
     assert ops.map_to_kv_tensors([PAGE]) and int(torch.count_nonzero(ts[0][PAGE // 2:PAGE])) == 0
     assert ops.unmap_from_kv_tensors([PAGE])
 
@@ -1249,10 +1249,10 @@ def test_shared_pool_between_two_processes(vmm, units):
         peer.start()
         ops.init_kvcached(DEV, PAGE, False)
         ts = ops.create_kv_tensors(16 * MiB, 2, DEV, 2, 2, 0, False)
-        assert (capi.get_option(129) > 0) == (units == "page_ids")
+        assert (capi.get_option(capi.OPT_LANES_PER_BUFFER) > 0) == (units == "page_ids")
         msg = q.get(timeout=180)
         assert msg == "ready", msg
-        i0 = capi.get_option(163)
+        i0 = capi.get_option(capi.OPT_IMPORTS_DIRECT)
         assert ops.map_to_kv_tensors([PAGE])
         epp = PAGE // 2
         k = 0
